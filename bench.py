@@ -39,6 +39,9 @@ legs        = (N = 1) one warm-up and one timed step each of the per-GPU shares 
 cpu_baseline= the CPU oracle (oracle/egdst_oracle.c, glibc math, gcc -O2) on a bounded sample of the same draws, timed in
               this run on the GPU box's host: one thread (`value`, `cores` = 1) and every core this process may use
               (scheduler affinity and cgroup quota), one process per core.
+--dump-outputs DIR: after the timed steps, what the last of them returned to its caller (objective, status and evaluation counts
+              per draw: see dump_outputs) as DIR/<name>.npy.  The draws are seeded, so the same arguments give the same inputs and
+              two builds can be compared output for output.
 """
 import argparse
 import json
@@ -367,6 +370,34 @@ def timed_leg(workload, ndraw, model=None, drawgen=None, params=None, label=None
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, objective, chunks, rank, world, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the last timed step handed its caller, for this rank's draws in order, as float64 .npy files:
+      objective       [n, 2]  value and consumption at the first endogenous grid point of (it=0, ist=0); 0 for a failed draw
+                              (the solver returns NaN there: its status says it failed, and every value written stays finite)
+      status          [n]     per-draw status (0 = solved; include/egdst.h error codes)
+      status_where    [n, 2]  period and state the status refers to
+      evals           [n]     evaluations the reference would count
+      evals_credited  [n]     evaluations accounted for without being executed
+    More draws than fit `limit` bytes (over all ranks): a fixed, seeded sample of them, whose indices go to draw_index.npy.
+    With several ranks every file name ends in _rank<r>."""
+    st, wh, ev, cr = (np.concatenate([c[k] for c in chunks]) for k in range(4))
+    objective = np.where((st != 0)[:, None], 0.0, objective)
+    arrays = {'objective': objective, 'status': st, 'status_where': wh, 'evals': ev, 'evals_credited': cr}
+    n = len(st)
+    per_draw = sum(8 * int(np.prod(a.shape[1:])) for a in arrays.values()) + 8
+    keep = max(1, limit // world // per_draw)
+    if n > keep:
+        idx = np.sort(np.random.default_rng(20241).choice(n, keep, replace=False))
+        arrays = dict({k: a[idx] for k, a in arrays.items()}, draw_index=idx)
+    os.makedirs(path, exist_ok=True)
+    suffix = '_rank%d' % rank if world > 1 else ''
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -385,7 +416,11 @@ def main():
     ap.add_argument('--no-extras', action='store_true', help='skip the copy-peak, export and estimation legs')
     ap.add_argument('--rehearse-legs', action='store_true', help='N > 1: the strong-scaling sub-records on reduced batches (C5 x 32, C4 x 8 draws): a plumbing rehearsal on one card, not a result')
     ap.add_argument('--no-legs', action='store_true', help='skip the legs of the stress configurations (C4 x 32, C5 x 128, C2 a0=0; N > 1: the strong-scaling batches)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned to its caller as DIR/<name>.npy (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
@@ -474,6 +509,8 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    last_chunks = []   # --dump-outputs: (status, where, evals, credited) of every chunk of the last timed step, as read in the step
+
     def run_step(s):
         """one step of this rank: every chunk of its shard through the one handle; returns the counters"""
         ev_ref = ev_exec = nfail = ndone = 0
@@ -481,9 +518,11 @@ def main():
             solver.set_params_dev(dev[s, c * chunk:(c + 1) * chunk].data_ptr())
             solver.solve_async()
             solver.sync(raise_on_error=False)
-            st, _ = solver.status()
+            st, wh = solver.status()
             per = solver.evals()[1]
             cred = solver.evals_credited()
+            if args.dump_outputs and s == nsteps_all - 1:
+                last_chunks.append((st[:valid], wh[:valid], per[:valid], cred[:valid]))
             ok = st[:valid] == 0
             ev_ref += int(per[:valid].sum())
             ev_exec += int((per[:valid] - cred[:valid])[ok].sum())
@@ -511,6 +550,8 @@ def main():
             step_ms.append((time.perf_counter() - ts_) * 1e3)   # (every step ends with a host sync: status and counts are read back)
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and mine_n:
+        dump_outputs(args.dump_outputs, obj[nsteps_all - 1, :mine_n].cpu().numpy(), last_chunks, rank, world)
 
     # the last step's draws once more with HIP events around every launch (16 streams), then with one draw group: outside the timed region
     kms, klaunch, algbytes = profiled_step(solver) if solver else (np.zeros(9), np.zeros(9, dtype=np.int32), 0)
