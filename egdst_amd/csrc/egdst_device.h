@@ -34,6 +34,7 @@ struct Geom {
 struct Batch {
     Geom g;
     int draw0;           // first schedule slot of the group this launch works on (groups run on their own streams)
+    int gdraws;          // draws of that group: its slices of fixlist, tplist and tpbiglist hold gdraws * MS_NST (* MS_ND) entries
     const int *order;    // [ndraw] schedule: slot -> draw (identity until the host re-balances, egdst_host.inc)
     struct Env1Tile *e1tiles;  // single-choice models: per (slot, state, tile) descriptors of k_env1
     unsigned *e1done;          // [ndraw*MS_NST] tiles of the cell that have finished (counts on over the periods of a solve)
@@ -130,6 +131,7 @@ struct ProbeOut {
     double A0;        // last guess before the grid stage
     double M0;        // M returned for it
     double evfa0;     // egdst_solver.c:430,593,643
+    double baseA, baseM;  // the generator's base point (egdst_solver.c:1086): k_fixup starts the stream from this hand-over
 };
 
 // ---- inverse normal cdf (Acklam), egdst_lib.c:435-519 ---------------------------------------

@@ -192,6 +192,8 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
     if (rows_cap < 0) return set_err(EGDST_E_ARG, "egdst_create_compact: rows_cap < 0");
     if (d->T < d->t0 || d->ngridm < 2 || d->ny < 1 || !d->quadrature || d->nthrhmax < 1)
         return set_err(EGDST_E_ARG, "egdst_create: inconsistent descriptor");
+    if ((long long)MS_NST * d->ny > 65535)  // a candidate's evaluation count is packed in 16 bits (eg_sc_pack) and read back as a result
+        return set_err(EGDST_E_ARG, "egdst_create: more than 65535 (next state, shock node) terms per evaluation");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
         return set_err(EGDST_E_NOGPU, "%s", egdst_strerror(EGDST_E_NOGPU));
@@ -609,6 +611,7 @@ static int batch_for_call(egdst_handle *h, const Batch **out)
         HIPCHK(hipStreamSynchronize(h->stream));  // (the staging entry may still be the source of an earlier upload)
         *slot = h->b;
         slot->draw0 = 0;
+        slot->gdraws = slot->g.ndraw;
         slot->sorted_valid = 0;
         HIPCHK(hipMemcpyAsync(h->b_dev + EGDST_MAX_GROUPS, slot, sizeof(Batch), hipMemcpyHostToDevice, h->stream));
         h->call_slot_ok = 1;
@@ -745,6 +748,7 @@ static int enqueue_solve(egdst_handle *h)
         for (int gi = 0; gi < G; gi++) {
             h->b_host[gi] = b;
             h->b_host[gi].draw0 = (G > 1) ? h->gstart[gi] : 0;
+            h->b_host[gi].gdraws = ((G > 1) ? h->gstart[gi + 1] : g.ndraw) - h->b_host[gi].draw0;
             h->b_host[gi].sorted_valid = sortcheck ? (int)((h->solve_seq & 0x3ffffu) << 12) + 1 : 0;
         }
         HIPCHK(hipMemcpyAsync(h->b_dev, h->b_host, sizeof(Batch) * G, hipMemcpyHostToDevice, s));

@@ -50,6 +50,9 @@
 #ifndef EG_SEQ_AFTER_RESEND  // k_fixup: guesses evaluated one at a time after a c1<=0 resend, before the next batch (with small batches: none
 #define EG_SEQ_AFTER_RESEND (FIX_LPG_SHIFT > 0 ? 0 : 1)  // -- C2 a0=-5 x 4096: 172.6 ms with one, 170.2 without; without small batches 0 or 1 were equal)
 #endif
+#ifndef EG_FIX_REUSE  // k_fixup starts a stream at the probe's hand-over and takes the grid kernel's rows while its guesses are the same
+#define EG_FIX_REUSE 1  // (0: the stream is regenerated from its first call, every guess evaluated again)
+#endif
 #ifndef FIX_BS  // threads of a k_fixup workgroup = guesses evaluated per batch of the sequential stream
 #define FIX_BS (4 * WAVE)  // one wave per SIMD: the sequential stretches run redundantly in every wave
 #endif
@@ -78,6 +81,17 @@ static __device__ __forceinline__ void eg_fail(BatchRef b, int draw, int it, int
         b.where[2 * draw] = it;
         b.where[2 * draw + 1] = ist;
     }
+}
+
+// Appends v to the group's list of `cap` entries (fixlist, tplist, tpbiglist): an index past the slice would write into the next
+// group's, so it is an internal error of the draw instead and nothing is written (readers take at most `cap` entries).
+static __device__ __forceinline__ void eg_list_push(BatchRef b, int *list, int *cnt, int cap, int v, int draw, int it, int ist)
+{
+    const unsigned k = atomicAdd((unsigned *)cnt, 1u);
+    if (k < (unsigned)cap)
+        list[k] = v;
+    else
+        eg_fail(b, draw, it, ist, EGDST_E_INTERNAL);
 }
 
 static __device__ __forceinline__ ms_env eg_env(BatchRef b, int draw)
@@ -420,6 +434,26 @@ static __device__ __forceinline__ int eg_wave_expectation(BatchRef b, const ms_e
     return status;
 }
 
+// k_fixup: did the grid kernel evaluate the generator's grid guess An for index n?  Its guess for n is eg_grid_A(GLg, 0, gA0, n);
+// then *w is the packed status word of that row.
+static __device__ __forceinline__ bool eg_fix_row(BatchRef b, const ms_env *E, const ms_pv *cur, const GridLims &GLg, double gA0, size_t co,
+                                                  int n, double An, int *w)
+{
+    if (n < 1 || n >= b.g.ngridm || !(An == eg_grid_A(E, cur, GLg, 0, gA0, n))) return false;
+    *w = b.cSt[co + n];
+    return true;
+}
+// ... the status of that row for the next guess (A_n from the exact A_{n-1} = last), 0x10000 if there is none
+static __device__ __forceinline__ int eg_fix_row_status(BatchRef b, const ms_env *E, const ms_pv *cur, double lim1, double lim2, double lim3,
+                                                        double lim3p, double k3, int ntogenerate, const GridLims &GLg, double gA0, size_t co,
+                                                        int n, double last)
+{
+    GridLims GL;
+    GL.lim1 = lim1, GL.lim2 = lim2, GL.lim3 = lim3, GL.lim3p = lim3p, GL.k3 = k3, GL.ntogenerate = ntogenerate;
+    int w = 0;
+    return eg_fix_row(b, E, cur, GLg, gA0, co, n, eg_grid_A(E, cur, GL, n - 1, last, n), &w) ? eg_sc_status(w) : 0x10000;
+}
+
 // The guess generator (adraw, egdst_solver.c:955-1159) run by one wave for one (draw, ist, id); all lanes carry
 // the same state and every expectation is evaluated cooperatively (eg_wave_expectation).
 //   full == 0 (k_probe): stop at the call that would emit the first point of the closed-form grid and hand the
@@ -501,8 +535,32 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
     int skipped = 0;   // calls of the stage-0 fixed point that were accounted for without being executed
     int seq_left = 0;  // full mode: grid guesses to evaluate one at a time before batching again
     int small = 0;     // full mode: the next batch is a small one (several lanes per guess), see the batch below
-#ifdef EGDST_FIXSTAT  // diagnostic: what a regeneration consists of (dbg ints 8..11, ticks in ints 12-13)
-    int fs_batches = 0, fs_single = 0, fs_resend = 0;
+    // k_fixup: the stream up to the probe's hand-over to the grid kernel is what k_probe computed (the generator is a pure function
+    // of the expectations it is given, and those of a period are fixed), so it starts there -- unless the probe kept more than the
+    // point at candidate 0 (the grid kernel wrote over the rest).  Then, until the stream's first resend, a grid guess that equals
+    // the grid kernel's guess for the same index bit for bit has its evaluation stored at candidate n: the row is taken instead of
+    // evaluated (`reuse`).  Rows are read before any write can reach them: with np <= 1 at the hand-over and one kept point per
+    // consumed guess, the kept points of the rows consumed so far land at or below those rows (np <= ngenerated) until a resend.
+    int reuse = 0, taken = 0;  // taken: grid rows consumed without an evaluation
+    GridLims GLg;  // the grid kernel's limits, from the probe's record; its guess n is eg_grid_A(GLg, 0, gA0, n)
+    GLg.lim1 = GLg.lim2 = GLg.lim3 = GLg.lim3p = GLg.k3 = 0, GLg.ntogenerate = 0;
+    double gA0 = 0;
+    if (full && EG_FIX_REUSE) {
+        const ProbeOut P0 = *P;
+        __syncthreads();  // (every thread has read the record before the lead thread rewrites it at the end of the stream)
+        if (P0.active && P0.grid && P0.np <= 1) {
+            ngenerated = 1, ncalls = P0.ncalls, keep = 1, ntogenerate = P0.ntogenerate, np = P0.np, nev = P0.probe_evals;
+            baseA = P0.baseA, baseM = P0.baseM, lim1 = P0.lim1, lim2 = P0.lim2, lim3 = P0.lim3, lim3p = P0.lim3p, k3 = P0.k3;
+            last = P0.A0, M = P0.M0, evfa0 = P0.evfa0;
+            GLg.lim1 = lim1, GLg.lim2 = lim2, GLg.lim3 = lim3, GLg.lim3p = lim3p, GLg.k3 = k3, GLg.ntogenerate = ntogenerate;
+            gA0 = last;
+            reuse = 1;
+        }
+    }
+#ifdef EGDST_FIXSTAT  // diagnostic: what a regeneration consists of (dbg ints 8..11, ticks in ints 12-13; 4 calls taken over from the
+    // probe, 7 guesses evaluated in batches, 14 grid rows taken)
+    int fs_batches = 0, fs_single = 0, fs_resend = 0, fs_evald = 0;
+    const int fs_head = reuse ? ncalls : 0;
     const unsigned long long fs_t0 = wall_clock64();
 #endif
 #ifdef EGDST_CENSUS
@@ -620,6 +678,7 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
                     break;
                 }
                 if (ncalls >= b.g.ngridmax) break;
+                reuse = 0;   // the guesses follow new limits from here on
                 EG_WSYNC();  // (every lane has read the history)
                 if (lane == 0) {
                     for (int q = 2; q > 0; q--) {
@@ -645,7 +704,9 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
                 // the next call either starts the closed-form grid (handled by k_grid) or ends the stream
                 grid = (M < mmax && ngenerated < ntogenerate) ? 1 : 0;
                 break;
-            } else if (full && seq_left > 0 && M < mmax && ngenerated < ntogenerate) {
+            } else if (full && M < mmax && ngenerated < ntogenerate &&
+                       (seq_left > 0 || (reuse && eg_fix_row_status(b, &E, &cur, lim1, lim2, lim3, lim3p, k3, ntogenerate, GLg, gA0, co,
+                                                                    ngenerated, last) == 1))) {
                 // Right after a resend the next guess often signals c1<=0 again (streams that re-base at every
                 // point exist): take the next few grid guesses one at a time, evaluated cooperatively below,
                 // before paying for a whole batch of speculative evaluations again.
@@ -655,7 +716,7 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
                 ngenerated += 1;
                 ncalls += 1;
                 keep = 1;
-                seq_left -= 1;
+                seq_left = max(seq_left - 1, 0);  // (a guess the grid kernel found signalling c1<=0: evaluated alone, for the resend)
             } else if (M < mmax && ngenerated < ntogenerate) {
                 // Grid stage of the sequential stream (:1100-1149), WAVE guesses at a time: lane l evaluates the
                 // guess the generator would emit l calls from now (serial shock loop inside the lane, as k_grid
@@ -666,9 +727,27 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
                 __shared__ unsigned long long sx_can[NW], sx_hard[NW], sx_neg[NW], sx_stop[NW], sx_kept[NW], sx_inf[NW];
                 __shared__ int sx_hst[NW], sx_cnt[NW], sx_bist;
                 __shared__ double sx_take[2], sx_neg4[3];
-#ifdef EGDST_FIXSTAT
-                fs_batches++;
+                __shared__ int sx_ntake[NW];
+                // the rows of the grid kernel: the run of guesses from the next one on that it evaluated and found normal (status 0,
+                // whose M, C, V and count are all stored) is consumed as a batch of its own, read instead of evaluated
+                int ntake = 0, tw = 0;
+                if (full && reuse) {
+                    const int gt = threadIdx.x, nt_ = ngenerated + gt;
+                    const bool ok = nt_ < ntogenerate && (ncalls + 1 + gt) < b.g.ngridmax &&
+                                    eg_fix_row(b, &E, &cur, GLg, gA0, co, nt_, eg_grid_A(&E, &cur, GL, ngenerated - 1, last, nt_), &tw) &&
+                                    eg_sc_status(tw) == 0;
+                    const unsigned long long nok = __ballot(!ok);
+                    if (lane == 0) sx_ntake[wave] = nok ? wave * WAVE + __ffsll((long long)nok) - 1 : NW * WAVE;
+                    __syncthreads();
+                    ntake = NW * WAVE;
+                    for (int w = 0; w < NW; w++) ntake = min(ntake, sx_ntake[w]);
+#ifdef EGDST_EMU
+                    if (ntake > 0 && np > ngenerated) {  // a kept point may have been written over a row about to be taken
+                        fprintf(stderr, "k_fixup: row %d taken after %d kept points\n", ngenerated, np);
+                        abort();
+                    }
 #endif
+                }
                 // Two shapes of a batch.  The regular one: a guess per lane, its (next state, shock node) terms one after the other inside
                 // the lane (as k_grid_lds does).  Right after a resend (small != 0) the next c1<=0 is usually a few points away -- a
                 // stream re-bases five times on average, nearly always within its first dozens of points -- and a whole batch of
@@ -676,16 +755,22 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
                 // lane per shock node as in k_grid_wide (eg_wave_expectation with groups of FIX_LPG: the same terms accumulated in
                 // the same order), WAVE / FIX_LPG guesses per wave -- a quarter of the latency.  A small batch that is consumed
                 // whole without a signal hands back to the regular shape.  Only the lane (lane % lpg) == 0 of a guess votes below.
-                const int lsh = small ? FIX_LPG_SHIFT : 0, lpg = 1 << lsh, gpw = WAVE >> lsh;  // lanes per guess, guesses per wave
+                const int lsh = (small && !ntake) ? FIX_LPG_SHIFT : 0, lpg = 1 << lsh, gpw = WAVE >> lsh;  // lanes per guess, guesses per wave
                 const bool rep = (lane & (lpg - 1)) == 0;
                 const int gl = wave * gpw + (lane >> lsh);  // position of this thread's guess in the batch
                 const int n = ngenerated + gl;              // value of `ngenerated` at this thread's call
-                const bool can = n < ntogenerate && (ncalls + 1 + gl) < b.g.ngridmax;
+                const bool can = n < ntogenerate && (ncalls + 1 + gl) < b.g.ngridmax && (!ntake || gl < ntake);
                 LaneEval r;
                 r.status = 0, r.cnt = 0, r.bist = 0, r.M = NAN, r.C = r.V = r.R = 0, r.bshock = r.bcash = 0;
                 double An = last;
                 if (can) {
                     An = eg_grid_A(&E, &cur, GL, ngenerated - 1, last, n);
+                    if (ntake) {  // (what eg_lane_eval returns for a normal point)
+                        r.cnt = eg_sc_count(tw);
+                        r.M = r.R = b.cM[co + n];
+                        r.C = b.cC[co + n];
+                        r.V = b.cV[co + n];
+                    } else
 #if FIX_LPG_SHIFT > 0
                     if (small) {
                         double rhs_ = 0, evf_ = 0;
@@ -740,6 +825,10 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
                 // guesses [0, take) are consumed as ordinary calls; a stopping point is itself consumed
                 const int take = (fneg <= fstop) ? fneg : min(fstop + 1, ncan);
                 const bool negnext = fneg <= fstop && fneg < ncan;  // the call after them hits c1<=0
+                if (ntake) taken += take;
+#ifdef EGDST_FIXSTAT
+                if (!ntake) fs_batches++, fs_evald += ncan;
+#endif
                 if (fhard >= 0 && (fhard < take || (negnext && fhard == fneg))) {
                     if (lead) eg_fail(b, draw, it, ist, hcode);
                     return;
@@ -807,6 +896,7 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
 #endif
                     small = FIX_LPG_SHIFT > 0 ? 1 : 0;
                     seq_left = EG_SEQ_AFTER_RESEND;
+                    reuse = 0;
                     ms_pv nb;
                     nb.it = it + 1;
                     nb.ist = sx_bist;
@@ -860,6 +950,7 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
             if (st == 1) {
                 small = (full && FIX_LPG_SHIFT > 0) ? 1 : 0;
                 seq_left = EG_SEQ_AFTER_RESEND;
+                reuse = 0;
                 ms_pv nb;
                 nb.it = it + 1;
                 nb.ist = bist;
@@ -903,12 +994,13 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
     }
 #ifdef EGDST_EMU
     if (lead && full && getenv("EGDST_TRACE_FIXUP"))
-        fprintf(stderr, "fixup end it=%d id=%d ncalls=%d ngen=%d np=%d last=%g M=%g nev=%d\n", it, id, ncalls, ngenerated, np, last, M, nev);
+        fprintf(stderr, "fixup end it=%d id=%d ncalls=%d ngen=%d np=%d last=%g M=%g nev=%d taken=%d\n", it, id, ncalls, ngenerated, np, last, M, nev, taken);
 #endif
 #ifdef EGDST_FIXSTAT
     if (lead && full) {
         atomicAdd(&b.dbg[16 * draw + 8], fs_batches), atomicAdd(&b.dbg[16 * draw + 9], fs_single);
         atomicAdd(&b.dbg[16 * draw + 10], fs_resend), atomicAdd(&b.dbg[16 * draw + 11], 1);
+        atomicAdd(&b.dbg[16 * draw + 4], fs_head), atomicAdd(&b.dbg[16 * draw + 7], fs_evald), atomicAdd(&b.dbg[16 * draw + 14], taken);
         atomicAdd((unsigned long long *)(b.dbg + 16 * draw) + 6, wall_clock64() - fs_t0);
     }
 #endif
@@ -938,6 +1030,8 @@ static __device__ __forceinline__ void eg_adraw_cycle(BatchRef b, int it, int dr
         P->A0 = last;
         P->M0 = M;
         P->evfa0 = evfa0;
+        P->baseA = baseA;
+        P->baseM = baseM;
     }
 }
 
@@ -990,16 +1084,16 @@ __global__ void __launch_bounds__(WAVE) k_fixup_scan(const Batch *bp_, int it, i
         }
         if (resend || ms) break;
     }
-    if (resend && lane == 0) list[atomicAdd((unsigned *)cnt, 1u)] = combo;
+    if (resend && lane == 0) eg_list_push(b, list, cnt, b.gdraws * MS_NST * MS_ND, combo, draw, it, ist);
 }
 
 #ifndef FIX_MINW
-#define FIX_MINW 1  // (3: at most 168 VGPRs, so that a k_fixup wave fits a SIMD beside two waves of the -DENV_MINW=3 k_envelope)
+#define FIX_MINW 2  // two workgroups per CU (<= 256 VGPRs); (3: at most 168 VGPRs, a k_fixup wave beside two waves of the -DENV_MINW=3 k_envelope)
 #endif
 __global__ void __launch_bounds__(FIX_BS, FIX_MINW) k_fixup(const Batch *bp_, int it, const int *cnt, const int *list)
 {
     BatchRef b = EG_BATCH_REF(bp_);
-    const int n = *cnt;
+    const int n = min(*cnt, b.gdraws * MS_NST * MS_ND);
     for (int k = blockIdx.x; k < n; k += gridDim.x) {
         const int combo = list[k];
         const int id = combo % MS_ND, ist = (combo / MS_ND) % MS_NST, draw = b.order[b.draw0 + combo / (MS_ND * MS_NST)];
@@ -3375,7 +3469,7 @@ __global__ void __launch_bounds__(ENV_MAXBS, ENV_MINW) ENV_VGPR_ATTR k_envelope(
 {
     BatchRef b = EG_BATCH_REF(bp_);
     // (ONE inlined copy of the cell's code: the other passes are the loop with a single turn)
-    const int n = (pass == 3) ? *cnt : (int)gridDim.x;
+    const int n = (pass == 3) ? min(*cnt, b.gdraws * MS_NST) : (int)gridDim.x;
     for (int k = blockIdx.x; k < n; k += gridDim.x) {
         eg_envelope_cell(b, it, terminal, lcap, pass == 3 ? 1 : pass, part, pass == 3 ? list[k] : k);
         __syncthreads();  // (the LDS of the cell is reused by the next one)
@@ -3786,7 +3880,7 @@ static __device__ __forceinline__ void tp_sort(BatchRef b, int it, int stage, in
             if (!big && biglist && nall <= bigcap) {  // the second tier's (nothing of the cell has been touched yet)
                 if (threadIdx.x == 0) {
                     b.defer[cell] = TP_BIG;
-                    biglist[atomicAdd((unsigned *)bigcnt, 1u)] = bx_;
+                    eg_list_push(b, biglist, bigcnt, b.gdraws * MS_NST, bx_, draw, it, ist);
                 }
                 return;
             }
@@ -3880,7 +3974,7 @@ __global__ void __launch_bounds__(TP_SORT_BS, TP_SORT_MINW) k_tp_sort(const Batc
     do {                                                                    \
         if (threadIdx.x == 0) {                                             \
             b.defer[cell] = (why);                                           \
-            list[atomicAdd((unsigned *)cnt, 1u)] = bx_;                     \
+            eg_list_push(b, list, cnt, b.gdraws * MS_NST, bx_, draw, it, ist); \
             atomicAdd(&b.tpstat[2 * draw + 1], 1u);                         \
         }                                                                   \
         return;                                                             \
@@ -3906,7 +4000,7 @@ static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, in
         const int df = TP_DEFERRED_UNIFORM(S, cell);
         if (df == TP_BIG && !big) return;  // the second tier of the stage decides about this cell (and lists it if it gives up)
         if (df) {
-            if (stage == 1 && tid == 0) list[atomicAdd((unsigned *)cnt, 1u)] = bx_, atomicAdd(&b.tpstat[2 * draw + 1], 1u);
+            if (stage == 1 && tid == 0) eg_list_push(b, list, cnt, b.gdraws * MS_NST, bx_, draw, it, ist), atomicAdd(&b.tpstat[2 * draw + 1], 1u);
             return;
         }
     }
@@ -4098,7 +4192,7 @@ __global__ void __launch_bounds__(TP_SORT_BS, TP_WALK_MINW) k_tp_big(const Batch
 {
     EG_DYN_LDS(dynlds);
     __shared__ TpShared S;
-    const int n = *bigcnt;
+    const int n = min(*bigcnt, EG_BATCH_REF(bp_).gdraws * MS_NST);
     for (int k = blockIdx.x; k < n; k += gridDim.x) {
         tp_sort(EG_BATCH_REF(bp_), it, 1, cap, cap, biglist[k], &S, (double *)dynlds, 1);
         __threadfence_block();  // (the sorted stream goes through global memory from one phase to the next)
