@@ -18,7 +18,6 @@ struct Env1Tile { unsigned long long desc, evals; };
 #define EG_NPROF 9      // kernel classes of egdst_get_profile
 #define EG_FIX_GRID 32  // workgroups of a k_fixup launch; they loop over the streams k_fixup_scan listed
 #define EG_ENV_TP_MIN_CELLS 512   // (draw, state) cells per solve from which the throughput path of the envelope step is used
-#define EG_ENV_TP_LONG_KEYS 4096  // sampled M keys a k_tp_sort workgroup stages for a stream too long for LDS (48 KB with the unused class words)
 #define EG_ENV_TP_REST_GRID 32    // workgroups of the k_envelope launch that does the cells the throughput path left over
 #define EG_ENV_TP_BIG_GRID 64     // workgroups of the second-tier launch of stage 1 (k_tp_big)
 #define EG_ENV_TP_MAX_KEYS 5120   // points of a stream that the kernels of the throughput path keep in LDS (k_tp_walk: 24 B each)
@@ -26,6 +25,31 @@ struct Env1Tile { unsigned long long desc, evals; };
 #define EG_TP_WALK_BS0 TP_WALK_BS  // threads of a stage-0 walk workgroup
 #endif
 #define EG_TP_WALK_LDS_PER_POINT 24  // k_tp_walk: M, V (8 B each), class word (4 B), function id and position list (2 B each)
+#include <optional>
+// Environment switches of the library (INTEGRATION.md), read once when a handle is created: unset (nullopt) means the
+// automatic choice, a set value is taken as atoi reads it.
+struct Options {
+    std::optional<int> noseg, lcap, groups, hwq, adaptive;   // EGDST_NOSEG, EGDST_LCAP, EGDST_GROUPS, GPU_MAX_HW_QUEUES, EGDST_ADAPTIVE
+    std::optional<int> grid_wide, grid_lds, grid_cv;         // EGDST_GRID_WIDE, EGDST_GRID_LDS, EGDST_GRID_CV
+    std::optional<int> env_tp, tp_lkcap, tp_sort_lkcap, tp_big, tp_bigcap;  // EGDST_ENV_TP, EGDST_TP_*
+    std::optional<int> e1_defer_all;                         // EGDST_E1_DEFER_ALL
+    bool no_env1, debug_sync, debug_poison;                  // set at all: EGDST_NO_ENV1, EGDST_DEBUG_SYNC, EGDST_DEBUG_POISON
+};
+// What the launches of a solve look like: fixed for a handle by its geometry, its options and the kernels' attributes.
+struct LaunchPlan {
+    bool grid_wide;      // a batch that leaves the GPU mostly idle spreads every grid point over 16 lanes (k_grid_wide)
+    int grid_lrows;      // LDS rows of M columns of k_grid_lds (0: the general k_grid)
+    bool grid_sampled;   // those rows are a sampled index of tables too long to stage whole
+    bool sortcheck;      // k_sortcheck before the probe (the sampled index needs ordered M columns)
+    bool grid_cv;        // k_grid_lds_cv: whole tables (M, C, V) in LDS
+    bool e1_on;          // single-choice models: k_env1 compacts the regular cells
+    int e1_defer_all;    // tests: k_env1 hands every cell to k_envelope (1: before its tiles write rows, 2: after)
+    bool env_parts;      // several choices: per-choice workgroups of k_envelope (off while the kink log is on)
+    bool env_tp;         // several choices: the throughput path of the envelope step (off while the kink log is on)
+    int tp_lkcap, tp_lkcap0, tp_scap0, tp_scap1, tp_bigcap;  // stream budgets of the throughput path's kernels
+    bool tp_big;         // second tier of stage 1 (k_tp_big)
+    int tp_walk_bs0;     // threads of a stage-0 walk workgroup
+};
 struct egdst_handle {
     Batch b;
     egdst_desc desc;
@@ -51,11 +75,10 @@ struct egdst_handle {
     double *h_par;     // pinned staging for parameters
     char *scratch_lo, *scratch_hi;  // work arrays that hold no state across periods (diagnostic poisoning)
     int profile;                    // record HIP events around every launch of each kernel
-    int lcap;                       // sorted points that fit k_envelope's dynamic LDS (large launch)
+    int lcap;                       // sorted points that fit k_envelope's dynamic LDS
     size_t lds_bytes;
-    hipGraphExec_t graph_exec;      // captured launch sequence of a solve (egdst_solve_async)
-    int graph_groups, graph_failed;
-    int lcap_small, two_pass;       // small launch (two workgroups per CU) + deferral of the cells that need more
+    Options opt;                    // environment switches, read at create
+    LaunchPlan plan;                // launch decisions of a solve, made at create
     hipEvent_t *ev;                 // [groups][EG_NPROF kernel classes][nt][2]
     int nev;
     // draw groups: contiguous ranges of draws whose per-period kernels run on their own streams, so that a
@@ -180,6 +203,123 @@ static hipError_t eg_reserve_envelope_lds(size_t bytes)
 }
 #endif
 
+// The only place that reads the environment.
+static Options read_options()
+{
+    auto num = [](const char *name) -> std::optional<int> {
+        const char *v = getenv(name);
+        if (!v) return std::nullopt;
+        return atoi(v);
+    };
+    Options o;
+    o.noseg = num("EGDST_NOSEG");
+    o.lcap = num("EGDST_LCAP");             // tests: a small value sends every stream down the global path
+    o.groups = num("EGDST_GROUPS");
+    o.hwq = num("GPU_MAX_HW_QUEUES");       // what the HIP runtime was started with
+    o.adaptive = num("EGDST_ADAPTIVE");
+    o.grid_wide = num("EGDST_GRID_WIDE");
+    o.grid_lds = num("EGDST_GRID_LDS");     // 0: the general k_grid
+    o.grid_cv = num("EGDST_GRID_CV");
+    o.env_tp = num("EGDST_ENV_TP");
+    o.tp_lkcap = num("EGDST_TP_LKCAP");     // tests: a small value exercises the sampled key index
+    o.tp_sort_lkcap = num("EGDST_TP_SORT_LKCAP");
+    o.tp_big = num("EGDST_TP_BIG");
+    o.tp_bigcap = num("EGDST_TP_BIGCAP");
+    o.e1_defer_all = num("EGDST_E1_DEFER_ALL");
+    o.no_env1 = getenv("EGDST_NO_ENV1") != nullptr;
+    o.debug_sync = getenv("EGDST_DEBUG_SYNC") != nullptr;     // diagnostic: name the kernel a fault belongs to
+    o.debug_poison = getenv("EGDST_DEBUG_POISON") != nullptr; // diagnostic: no kernel may rely on stale work arrays
+    return o;
+}
+
+static LaunchPlan plan_launches(const Geom &g, const Options &o)
+{
+    LaunchPlan p = {};
+    p.grid_wide = o.grid_wide ? *o.grid_wide != 0 : (long long)g.ndraw * MS_NST * MS_ND * g.ngridm <= EG_GRID_WIDE_MAX_POINTS;
+    // rows of next-period M columns a k_grid_lds workgroup stages (dynamic LDS): room for the regular points of every
+    // next state plus the kinks an envelope adds; a period whose tables need more falls back to the general path by itself
+    const long long lrows_all = (long long)MS_NST * (g.ngridm + g.ngridm / 2 + 64);
+    int grid_lrows = (int)(lrows_all < EG_GRID_LROWS_MAX ? lrows_all : EG_GRID_LROWS_MAX);
+    if (o.grid_lds) grid_lrows = *o.grid_lds;
+    if (MS_NST * 4 > grid_lrows) grid_lrows = 0;
+    p.grid_sampled = lrows_all > (long long)grid_lrows;
+    // A sampled index is staged with strided global reads by a workgroup that evaluates 256 points only: a coarser one is
+    // cheaper to stage than its longer window search costs.  Measured (rows: C4 x 32 draws / C5 x 128 draws per step):
+    // 16384: 168 ms / 14.0 s, 8192: 100 ms / 7.7 s, 4096: 73 ms / 4.82 s, 2048: 64 ms / 4.32 s, 1024: 65 ms / 4.45 s,
+    // 512: 65 ms / 4.59 s.  (More points per workgroup instead: the loop costs 32 VGPRs and two waves of occupancy, 78 ms.)
+    // (round 4, workgroups of 1024 points -- the C4 batch build -- share an index among four times the points: 3072 rows, 46.3 ms against
+    //  47.1 for C4 x 32; 4096: 46.5, 1024: 47.7.  C5 x 128 at 256 points per workgroup: 2048 rows 3.31 s, 4096: 4.35 s, 1024: 3.39 s.)
+    const int sampled_rows = (GRID_BS >= 1024) ? EG_GRID_SAMPLED_ROWS * 3 / 2 : EG_GRID_SAMPLED_ROWS;
+    if (p.grid_sampled && !o.grid_lds && grid_lrows > sampled_rows) grid_lrows = sampled_rows;
+#ifdef EGDST_EMU
+    if (grid_lrows > 20480) grid_lrows = 20480;
+#endif
+    p.grid_lrows = grid_lrows;
+    // tables that may not fit the LDS whole: the sampled form of k_grid_lds needs to know that their M columns are in order
+    // (k_sortcheck), and with that knowledge the expectations of k_probe / k_fixup need one bracket search instead of two
+    p.sortcheck = !p.grid_wide && grid_lrows > 0 && p.grid_sampled && g.nt < 4095;  // (the stamps hold the period in 12 bits)
+    // whole tables (M, C, V) in LDS when they fit 48 KB (k_grid_lds_cv)
+    p.grid_cv = !p.grid_sampled && grid_lrows > 0 && 24 * (long)grid_lrows <= 48 * 1024 &&
+                (o.grid_cv ? *o.grid_cv != 0 : EG_GRID_CV_DEFAULT != 0);
+#if MS_ND == 1
+    // single-choice models: the regular cells are compacted by many workgroups (k_env1_*), k_envelope takes the rest
+    p.e1_on = !o.no_env1;
+    p.e1_defer_all = o.e1_defer_all ? (*o.e1_defer_all == 2 ? 2 : 1) : 0;
+    // (the throughput path is for models with several choices: env_tp stays false)
+#else
+    // several choices: the choice lists and their secondary envelopes as workgroups of their own (part 1), then the primary
+    // envelope per cell (part 2); one workgroup per cell (part 0) when the kink log is on (its rows are ordered) -- for
+    // batches that leave CUs idle (measured: C3 single solve 42 -> 25 ms; C2 x 4096 274 -> 300 ms, where a workgroup
+    // that only compacts a list still takes a CU's LDS)
+    p.env_parts = g.ndraw * MS_NST <= EG_ENV_WIDE_MAX_CELLS;
+    // Batches with many cells per period: the throughput path (k_tp_*: five lean kernels, one wave per walk, streams in global
+    // memory) does the regular cells, k_envelope (pass 1) the cells it left flagged in b.defer.  Not for the terminal period
+    // (one of nt), not with the kink log (its rows are ordered per cell), not for streams that a single wave should not walk
+    // alone (C5: 65 536 points per stream and few cells -- there the segmented walk of k_envelope is the right tool).
+    // points of a stream the kernels keep in LDS, per stage: a folded choice list with its extrapolation points (stage 0), the
+    // lists of all choices (stage 1); the kinks of the envelopes add a few rows each.  Longer streams -- degenerate guess
+    // streams -- are left to k_envelope.  (LDS per workgroup decides how many walks share a CU: measured on C2 x 4096,
+    // 2100 entries 201.7 ms, 2314: 209.8 ms, 3000: 225 ms.)
+    const long tp_keys = (long)MS_ND * g.ngridm + (long)g.ngridm / 10 + 64;
+    const long tp_keys0 = (long)g.ngridm + (long)g.ngridm / 8 + 64;
+    // (Measured slower and removed: the walks of streams too long for the walk's LDS (C5, C3) over global memory,
+    //  k_tp_walk_g -- C5 x 128 3.89 s against 3.75 s, C3 x 64 51.5 against 37.7 ms, C5 x 16 720 against 763 ms.)
+    p.env_tp = o.env_tp ? *o.env_tp != 0 : ((long)g.ndraw * MS_NST >= EG_ENV_TP_MIN_CELLS && tp_keys <= EG_ENV_TP_MAX_KEYS);
+    int tp_lkcap = (int)(tp_keys < EG_ENV_TP_MAX_KEYS ? tp_keys : EG_ENV_TP_MAX_KEYS);
+#ifndef EGDST_EMU
+    {   // three walks per CU where a slightly smaller stream budget buys that (C2: 2164 -> ~2060 points, streams hold ~2010)
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, (const void *)k_tp_walk) == hipSuccess) {
+            const long cap3 = ((long)160 * 1024 / 3 - (long)fa.sharedSizeBytes - 512) / EG_TP_WALK_LDS_PER_POINT;
+            if (tp_lkcap > cap3 && cap3 >= (long)MS_ND * g.ngridm + 24) tp_lkcap = (int)cap3;
+        }
+    }
+#else
+    if (tp_lkcap > 6500) tp_lkcap = 6500;  // (the harness' static stand-in for the dynamic LDS, with its poisoned gaps)
+#endif
+    if (o.tp_lkcap) tp_lkcap = *o.tp_lkcap;
+    p.tp_lkcap = tp_lkcap;
+    p.tp_lkcap0 = (int)(tp_keys0 < tp_lkcap ? tp_keys0 : tp_lkcap);
+    // tests: so few keys that the sorts work on a sampled index of them and write the permutation through global memory
+    const int tp_skcap = o.tp_sort_lkcap.value_or(0);
+    p.tp_scap0 = tp_skcap ? tp_skcap : p.tp_lkcap0;
+    p.tp_scap1 = tp_skcap ? tp_skcap : tp_lkcap;
+    // second tier of stage 1: lists beyond the regular stream budget that still fit the largest one (EGDST_TP_BIG=0: off, such
+    // cells are k_envelope's as in round 3)
+    int tp_bigcap = (int)(tp_keys * 2 < EG_ENV_TP_MAX_KEYS ? tp_keys * 2 : EG_ENV_TP_MAX_KEYS);
+#ifdef EGDST_EMU
+    if (tp_bigcap > 6500) tp_bigcap = 6500;
+#endif
+    if (o.tp_bigcap) tp_bigcap = *o.tp_bigcap;
+    if (tp_bigcap > EG_ENV_TP_MAX_KEYS) tp_bigcap = EG_ENV_TP_MAX_KEYS;  // (what the kernels' dynamic LDS is reserved for)
+    p.tp_bigcap = tp_bigcap;
+    p.tp_big = !tp_skcap && tp_bigcap > tp_lkcap && tp_bigcap < 65536 && (o.tp_big ? *o.tp_big != 0 : true);
+    // threads of a stage-0 walk workgroup (all load the stream, its waves walk segments of it); stage 1 uses TP_WALK_BS
+    p.tp_walk_bs0 = (EG_TP_WALK_BS0 < WAVE || EG_TP_WALK_BS0 > TP_WALK_BS || EG_TP_WALK_BS0 % WAVE) ? TP_WALK_BS : EG_TP_WALK_BS0;
+#endif
+    return p;
+}
+
 extern "C" int egdst_create(const egdst_desc *d, int ndraw, int keep_history, void *stream, egdst_handle **out)
 {
     return egdst_create_compact(d, ndraw, keep_history, 0, stream, out);
@@ -216,7 +356,9 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
     g.mmax = d->mmax;
     g.a0 = d->a0;
     h->keep_history = keep_history;
-    h->b.noseg = getenv("EGDST_NOSEG") ? atoi(getenv("EGDST_NOSEG")) : 0;
+    h->opt = read_options();
+    h->plan = plan_launches(g, h->opt);
+    h->b.noseg = h->opt.noseg.value_or(0);
     if (stream) {
         h->stream = (hipStream_t)stream;
     } else {
@@ -303,13 +445,11 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
         off += align_up(items[i].bytes);
     }
 #endif
-    {   // dynamic LDS of k_envelope, 32 B per sorted point (M, C, V, class word, 16-bit function id and position).
-        // Large: room for 1.5x the regular points of all choices, at most ~150 KiB (one workgroup per CU).
-        // Small: what lets two workgroups share the 160 KiB of a CU next to the kernel's static LDS; cells whose
-        // stream does not fit are deferred to a second launch with the large size.
+    {   // dynamic LDS of k_envelope, 32 B per sorted point (M, C, V, class word, 16-bit function id and position):
+        // room for 1.5x the regular points of all choices, at most ~150 KiB (one workgroup per CU)
         long want = (long)MS_ND * g.ngridm * 3 / 2 + 64;
         if (want > 4200) want = 4200;  // 131 KB next to the 26 KB of static bookkeeping arrays
-        if (getenv("EGDST_LCAP")) want = atoi(getenv("EGDST_LCAP"));  // tests: a small value sends every stream down the global path
+        if (h->opt.lcap) want = *h->opt.lcap;
 #ifndef EGDST_EMU
         {   // what the kernel's own static arrays leave of the CU's 160 KiB
             hipFuncAttributes fa;
@@ -321,11 +461,8 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
 #endif
         h->lcap = (int)want;
         h->lds_bytes = (size_t)h->lcap * 32;
-        // Two-launch variant (EGDST_TWO_PASS=1, off by default): a first launch with lcap_small so that two workgroups
-        // share a CU, cells that need more are deferred to a second launch.  Measured slower on MI355X (two
-        // co-resident walks cost each other ~1.55x, DESIGN.md §5); kept for experiments and covered by the harness.
-        h->lcap_small = getenv("EGDST_LCAP_SMALL") ? atoi(getenv("EGDST_LCAP_SMALL")) : 2040;
-        h->two_pass = getenv("EGDST_TWO_PASS") && atoi(getenv("EGDST_TWO_PASS")) && h->lcap_small > 0 && h->lcap > h->lcap_small;
+        // (Measured slower and removed: a first launch with a small LDS budget so that two workgroups share a CU, the
+        //  cells that need more deferred to a second launch -- two co-resident walks cost each other ~1.55x, DESIGN.md §5.)
 #ifndef EGDST_EMU
         HIPCHK_H(eg_reserve_envelope_lds(h->lds_bytes));
 #if MS_ND > 1
@@ -347,16 +484,14 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
     HIPCHK_H(hipHostMalloc((void **)&h->b_host, sizeof(Batch) * (EGDST_MAX_GROUPS + 1)));
     h->ngroups = 1;
     {
-        const char *ge = getenv("EGDST_GROUPS");
-        const char *qe = getenv("GPU_MAX_HW_QUEUES");  // what the HIP runtime was started with (default 4)
-        const int hwq = qe ? atoi(qe) : 4;
+        const int hwq = h->opt.hwq.value_or(4);  // (the HIP runtime's default)
         // measured on MI355X (DESIGN.md §5): 8 groups need their own hardware queues to pay off
         const long cells = (long)ndraw * MS_NST;  // k_envelope workgroups per period
-        int want = ge ? atoi(ge)
-                      : (hwq >= 10 ? (cells >= 1024 && hwq >= 20 ? 16 : (cells >= 512 ? 8 : (cells >= 64 ? 4 : 1)))
-                                   : (cells >= 1024 ? 4 : 1));
+        int want = h->opt.groups ? *h->opt.groups
+                                 : (hwq >= 10 ? (cells >= 1024 && hwq >= 20 ? 16 : (cells >= 512 ? 8 : (cells >= 64 ? 4 : 1)))
+                                              : (cells >= 1024 ? 4 : 1));
         h->hwq = hwq;
-        h->adaptive = getenv("EGDST_ADAPTIVE") ? atoi(getenv("EGDST_ADAPTIVE")) : 1;
+        h->adaptive = h->opt.adaptive.value_or(1);
         h->order_h = (int *)malloc(sizeof(int) * ndraw);
         h->work_h = (unsigned *)malloc(sizeof(unsigned) * ndraw);
         h->strag_h = (unsigned char *)calloc(ndraw, 1);
@@ -469,10 +604,6 @@ static int build_schedule(egdst_handle *h)
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync((void *)h->b.order, h->order_h, sizeof(int) * nd, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));  // (order_h is reused by the next rebuild)
-    if (h->graph_exec) {  // a captured launch sequence is tied to the group ranges
-        (void)hipGraphExecDestroy(h->graph_exec);
-        h->graph_exec = nullptr;
-    }
     return 0;
 }
 
@@ -564,7 +695,6 @@ extern "C" int egdst_destroy(egdst_handle *h)
     free(h->order_h);
     free(h->work_h);
     free(h->strag_h);
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     for (int g = 0; g < EGDST_MAX_GROUPS; g++) {
         if (h->gstream[g]) (void)hipStreamDestroy(h->gstream[g]);
         if (h->join_ev[g]) (void)hipEventDestroy(h->join_ev[g]);
@@ -597,8 +727,6 @@ extern "C" int egdst_set_params_dev(egdst_handle *h, const double *params_dev, i
     return 0;
 }
 
-static int enqueue_solve(egdst_handle *h);
-
 // The device copy of the Batch that launches outside a solve read (simulator, accessor, checksums, objective): the handle's
 // current pointers, identity schedule range.  Enqueued on the handle's stream ahead of the kernel that reads it.
 // The slot is uploaded when it is first needed and again whenever the handle's Batch has changed (egdst_set_dbgout; `call_slot_ok`):
@@ -620,56 +748,152 @@ static int batch_for_call(egdst_handle *h, const Batch **out)
     return 0;
 }
 
-// The launch sequence of a solve never changes for a handle (same kernels, same arguments, same pool), so it is
-// captured once into a hipGraph -- memsets, the fork to the group streams, every period's kernels, the join -- and
-// replayed with one hipGraphLaunch: the host enqueues 1 node instead of ~5 launches per period and group, and the
-// dependent kernels of a period follow each other without a host round trip.  Measured on MI355X: 19.4 ms against
-// 19.6 ms for a single C2 solve and nothing for batches (the kernels are long, the launches already asynchronous),
-// so it is compiled only into diagnostic builds (-DEGDST_WITH_GRAPH, then EGDST_GRAPH=1 turns it on) and never used while HIP events
-// are being recorded or a diagnostic mode is on.
-extern "C" int egdst_solve_async(egdst_handle *h)
+// One group's launches of one period: its stream, its device copy of the Batch and its range of the schedule.
+struct GroupStep {
+    egdst_handle *h;
+    int gi, it;
+    hipStream_t gs;
+    const Batch *bg;
+    int draw0, gdraws;
+};
+
+// profiling: class k in {0 probe/terminal, 1 the grid kernel, 2 k_envelope, 3 regeneration (k_fixup_scan + k_fixup), and the
+// kernels of the envelope step's throughput path: 4 k_tp_prep, 5 / 6 k_tp_sort stage 0 / 1, 7 / 8 k_tp_walk stage 0 / 1};
+// events on the stream the kernels are launched on, [groups][EG_NPROF][nt][before, end]
+// (events are created when first recorded: a handle uses a fraction of the groups x classes x periods x 2 slots, and the
+//  runtime's pool of timed events is finite -- 46 080 of them at once failed with "invalid resource handle")
+static void eg_rec(const GroupStep &s, int k, int which)
 {
-    if (!h) return set_err(EGDST_E_ARG, "null handle");
-    if (!h->params_set && MS_NPARAM) return set_err(EGDST_E_ARG, "egdst_solve: parameters not set");
-#if !defined(EGDST_EMU) && defined(EGDST_WITH_GRAPH)  // (diagnostic builds only: measured slower, see above)
-    const char *ge = getenv("EGDST_GRAPH");
-    const bool want_graph = (ge ? atoi(ge) != 0 : false) && !h->profile && !getenv("EGDST_DEBUG_SYNC") && !getenv("EGDST_DEBUG_POISON");
-    if (want_graph && !h->graph_failed) {
-        if (h->graph_exec && h->graph_groups != h->ngroups) {
-            (void)hipGraphExecDestroy(h->graph_exec);
-            h->graph_exec = nullptr;
-        }
-        if (!h->graph_exec) {
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                const int rc = enqueue_solve(h);
-                e = hipStreamEndCapture(h->stream, &graph);
-                if (rc) e = hipErrorUnknown;
-            }
-            if (e == hipSuccess) e = hipGraphInstantiate(&h->graph_exec, graph, nullptr, nullptr, 0);
-            if (graph) (void)hipGraphDestroy(graph);
-            if (e != hipSuccess) {  // fall back to plain launches for the life of the handle
-                (void)hipGetLastError();
-                h->graph_exec = nullptr;
-                h->graph_failed = 1;
-            }
-            h->graph_groups = h->ngroups;
-        }
-        if (h->graph_exec) {
-            HIPCHK(hipGraphLaunch(h->graph_exec, h->stream));
-            h->solved = 1;
-            return 0;
-        }
-    }
-#endif
-    return enqueue_solve(h);
+    if (!s.h->profile) return;
+    hipEvent_t &e = s.h->ev[(((size_t)s.gi * EG_NPROF + k) * s.h->b.g.nt + s.it) * 2 + which];
+    if (!e) (void)hipEventCreate(&e);
+    if (e) (void)hipEventRecord(e, s.gs);
+}
+static void eg_before(const GroupStep &s, int k) { eg_rec(s, k, 0); }
+static void eg_end(const GroupStep &s, int k) { eg_rec(s, k, 1); }
+// EGDST_DEBUG_SYNC: wait for the launches so far and name them with the error they left
+static void eg_after(const GroupStep &s, const char *name)
+{
+    if (!s.h->opt.debug_sync) return;
+    hipError_t e = hipStreamSynchronize(s.gs);
+    fprintf(stderr, "[egdst] %s it=%d -> %s\n", name, s.it, hipGetErrorString(e));
+    fflush(stderr);
 }
 
+// The grid kernel of one group and period.
+static void enqueue_grid(const GroupStep &s, int combos)
+{
+    const LaunchPlan &p = s.h->plan;
+    const Geom &g = s.h->b.g;
+    const dim3 grid((g.ngridm - 1 + GRID_BS - 1) / GRID_BS, combos);
+    if (p.grid_wide)
+        hipLaunchKernelGGL(k_grid_wide, dim3(((g.ngridm - 1) * EG_GW + EG_GRIDW_BS - 1) / EG_GRIDW_BS, combos), dim3(EG_GRIDW_BS), 0,
+                           s.gs, s.bg, s.it);
+    else if (p.grid_lrows > 0 && p.grid_cv)
+        hipLaunchKernelGGL(k_grid_lds_cv, grid, dim3(GRID_BS), 3 * sizeof(double) * (size_t)p.grid_lrows, s.gs, s.bg, s.it, p.grid_lrows);
+    else if (p.grid_lrows > 0)
+        hipLaunchKernelGGL(k_grid_lds, grid, dim3(GRID_BS), sizeof(double) * (size_t)p.grid_lrows, s.gs, s.bg, s.it, p.grid_lrows);
+    else
+        hipLaunchKernelGGL(k_grid, grid, dim3(GRID_BS), 0, s.gs, s.bg, s.it);
+    // (Measured slower and removed: several asset points per lane, k_grid_lds_n -- C2 x 4096 194.4 ms against 184.8 with a
+    //  lane per point, C4 x 32 52.6 against 51.5, C5 x 128 3.72 s either way: 133 VGPRs, three waves per SIMD instead of six to eight.)
+}
+
+#if MS_ND > 1
+static size_t tp_sort_lds(int cap)  // keys, class words, and the permutation at the next power of two (k_tp_sort)
+{
+    int p2 = 1;
+    while (p2 < cap) p2 <<= 1;
+    return (size_t)12 * cap + (size_t)2 * p2 + 64;
+}
+#endif
+
+// The envelope step of one group and period (terminal: the last period).  env_tp / env_parts: the plan's choices, off while
+// the kink log is on.  Profiling class 2, or on the throughput path its kernels one by one.
+static void enqueue_envelope(const GroupStep &s, int terminal, bool env_tp, bool env_parts)
+{
+    egdst_handle *h = s.h;
+    const LaunchPlan &p = h->plan;
+    const Batch &b = h->b;
+    const int it = s.it;
+    const unsigned nc = (unsigned)(s.gdraws * MS_NST);  // cells of the group
+#if MS_ND == 1
+    (void)env_tp, (void)env_parts;
+    eg_before(s, 2);
+    if (p.e1_on) {
+        const int e1_nb = (int)EG_E1_NB(b.g.ngridm);
+        hipLaunchKernelGGL(k_env1, dim3(e1_nb, nc), dim3(E1_BS), 0, s.gs, s.bg, it, terminal, b.e1tiles, b.e1done, e1_nb, (unsigned)(it + 1),
+                           p.e1_defer_all);
+        hipLaunchKernelGGL(k_envelope, dim3(nc), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 1, 0, (const int *)nullptr,
+                           (const int *)nullptr);
+    } else
+        hipLaunchKernelGGL(k_envelope, dim3(nc), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 2, 0, (const int *)nullptr,
+                           (const int *)nullptr);
+    eg_end(s, 2);
+#else
+    if (env_tp && !terminal) {
+        int *tcnt = b.tpn + (size_t)s.gi * b.g.nt + it, *tlist = b.tplist + (size_t)s.draw0 * MS_NST;
+        int *bigc = b.tpbign + (size_t)s.gi * b.g.nt + it, *bigl = b.tpbiglist + (size_t)s.draw0 * MS_NST;
+        eg_before(s, 4);
+        hipLaunchKernelGGL(k_tp_prep, dim3(nc * MS_ND), dim3(TP_BS), 0, s.gs, s.bg, it);
+        eg_end(s, 4);
+        eg_before(s, 5);
+        hipLaunchKernelGGL(k_tp_sort, dim3(nc * MS_ND), dim3(TP_SORT_BS), tp_sort_lds(p.tp_scap0), s.gs, s.bg, it, 0, p.tp_scap0, p.tp_lkcap0, 0,
+                           (int *)nullptr, (int *)nullptr);
+        eg_end(s, 5);
+        eg_before(s, 7);
+        hipLaunchKernelGGL(k_tp_walk, dim3(nc * MS_ND), dim3(p.tp_walk_bs0), (size_t)EG_TP_WALK_LDS_PER_POINT * p.tp_lkcap0, s.gs, s.bg, it, 0,
+                           tlist, tcnt, p.tp_lkcap0);
+        eg_end(s, 7);
+        eg_before(s, 6);
+        hipLaunchKernelGGL(k_tp_sort, dim3(nc), dim3(TP_SORT_BS), tp_sort_lds(p.tp_scap1), s.gs, s.bg, it, 1, p.tp_scap1, p.tp_lkcap,
+                           p.tp_big ? p.tp_bigcap : 0, p.tp_big ? bigl : (int *)nullptr, p.tp_big ? bigc : (int *)nullptr);
+        eg_end(s, 6);
+        eg_before(s, 8);
+        hipLaunchKernelGGL(k_tp_walk, dim3(nc), dim3(TP_WALK_BS), (size_t)EG_TP_WALK_LDS_PER_POINT * p.tp_lkcap, s.gs, s.bg, it, 1, tlist, tcnt,
+                           p.tp_lkcap);
+        if (p.tp_big) {
+            const unsigned ng = nc < (unsigned)EG_ENV_TP_BIG_GRID ? nc : (unsigned)EG_ENV_TP_BIG_GRID;
+            const size_t walk_lds = (size_t)EG_TP_WALK_LDS_PER_POINT * p.tp_bigcap;
+            const size_t lds = tp_sort_lds(p.tp_bigcap) > walk_lds ? tp_sort_lds(p.tp_bigcap) : walk_lds;
+            hipLaunchKernelGGL(k_tp_big, dim3(ng), dim3(TP_SORT_BS), lds, s.gs, s.bg, it, tlist, tcnt, p.tp_bigcap, (const int *)bigl,
+                               (const int *)bigc);
+        }
+        eg_end(s, 8);
+        eg_before(s, 2);
+        hipLaunchKernelGGL(k_envelope, dim3(nc < (unsigned)EG_ENV_TP_REST_GRID ? nc : (unsigned)EG_ENV_TP_REST_GRID), dim3(ENV_MAXBS),
+                           h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 3, 0, (const int *)tlist, (const int *)tcnt);
+        eg_end(s, 2);
+        return;
+    }
+    eg_before(s, 2);
+    if (env_parts) {
+        hipLaunchKernelGGL(k_envelope, dim3(nc * MS_ND), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 2, 1,
+                           (const int *)nullptr, (const int *)nullptr);
+        hipLaunchKernelGGL(k_envelope, dim3(nc), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 2, 2, (const int *)nullptr,
+                           (const int *)nullptr);
+    } else
+        hipLaunchKernelGGL(k_envelope, dim3(nc), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 2, 0, (const int *)nullptr,
+                           (const int *)nullptr);
+    eg_end(s, 2);
+    // (Measured and removed in round 4: a SLOW LANE per group -- the cells whose guess streams k_fixup has to regenerate, 3 % of the
+    //  cells of a C2 a0 = -5 period and 57 of the 172 ms of every group's chain (the regeneration itself, and the secondary envelope of a
+    //  re-based stream: a dozen nearly coincident pieces, the slowest of a launch's 270 walks at 0.4 ms against a mean of 42 us), taken
+    //  out of the period's launches and done by list-driven launches on a second stream of the group, the two meeting only before the
+    //  period's last kernel.  Bit-exact, and 348 ms per solve against 168 with 16 groups, 224 with 10, 237 with 8: two cross-stream event
+    //  dependencies per group and period (1 900 per solve) cost far more on this runtime than the overlap returns -- the same finding as
+    //  round 3's side stream for k_fixup alone.)
+#endif
+}
+
+// Enqueues a solve on the handle's stream: the memsets, the fork to the group streams, every period's kernels per group (the
+// plan of the handle), the join.  (Measured and removed: capturing this sequence once into a hipGraph and replaying
+// it -- 19.4 ms against 19.6 ms for a single C2 solve and nothing for batches; the launches are already asynchronous.)
 static int enqueue_solve(egdst_handle *h)
 {
     Batch &b = h->b;
     const Geom &g = b.g;
+    const LaunchPlan &p = h->plan;
     hipStream_t s = h->stream;
     HIPCHK(hipMemsetAsync(b.status, 0, sizeof(int) * g.ndraw, s));
     HIPCHK(hipMemsetAsync(b.where, 0, sizeof(int) * 2 * g.ndraw, s));
@@ -679,52 +903,7 @@ static int enqueue_solve(egdst_handle *h)
     HIPCHK(hipMemsetAsync(b.algbytes, 0, sizeof(unsigned long long) * g.ndraw, s));
     HIPCHK(hipMemsetAsync(b.tlen, 0, sizeof(int) * (size_t)g.nslots * g.ndraw * MS_NST, s));
     HIPCHK(hipMemsetAsync(b.tthlen, 0, sizeof(int) * (size_t)g.nslots * g.ndraw * MS_NST, s));
-    const bool dbgsync = getenv("EGDST_DEBUG_SYNC") != nullptr;  // diagnostic: name the kernel a fault belongs to
-    // diagnostic (tests/diag/gpu_marginal.py): launch a kernel class TWICE -- the second launch recomputes what the first wrote -- to
-    // read the marginal cost of the class off the step time of the 16-stream batch.  bits: 1 k_probe, 2 the grid kernel, 4 k_tp_prep,
-    // 8 k_tp_sort stage 0, 16 k_tp_sort stage 1.  (NOT the walks: stage 0 rewrites its own input, and a repeated stage 1 lists a
-    // left-over cell twice -- two workgroups of k_envelope then work on the same cell at once; tried in round 4 on C2 a0 = 0: +13 ms, and
-    // on a0 = -5 it ended in a memory fault)
-    const int dbl = getenv("EGDST_DIAG_DOUBLE") ? atoi(getenv("EGDST_DIAG_DOUBLE")) : 0;
-    const int fix_grid = getenv("EGDST_FIX_GRID") ? atoi(getenv("EGDST_FIX_GRID")) : EG_FIX_GRID;  // workgroups of a k_fixup launch
-    const bool poison = getenv("EGDST_DEBUG_POISON") != nullptr;  // diagnostic: no kernel may rely on stale work arrays
-    const int G = (dbgsync || poison) ? 1 : h->nlanes;
-    // a batch that leaves the GPU mostly idle spreads every grid point over 16 lanes (k_grid_wide)
-    const bool grid_wide = (getenv("EGDST_GRID_WIDE") ? atoi(getenv("EGDST_GRID_WIDE")) != 0 : (long long)g.ndraw * MS_NST * MS_ND * g.ngridm <= EG_GRID_WIDE_MAX_POINTS);
-    // rows of next-period M columns a k_grid_lds workgroup stages (dynamic LDS): room for the regular points of every
-    // next state plus the kinks an envelope adds; a period whose tables need more falls back to the general path by itself
-    int grid_lrows = (int)((long long)MS_NST * (g.ngridm + g.ngridm / 2 + 64) < EG_GRID_LROWS_MAX
-                               ? (long long)MS_NST * (g.ngridm + g.ngridm / 2 + 64) : EG_GRID_LROWS_MAX);
-    if (getenv("EGDST_GRID_LDS")) grid_lrows = atoi(getenv("EGDST_GRID_LDS"));   // 0: the general k_grid
-    if (MS_NST * 4 > grid_lrows) grid_lrows = 0;
-    const bool grid_sampled = (long long)MS_NST * (g.ngridm + g.ngridm / 2 + 64) > (long long)grid_lrows;
-    // A sampled index is staged with strided global reads by a workgroup that evaluates 256 points only: a coarser one is
-    // cheaper to stage than its longer window search costs.  Measured (rows: C4 x 32 draws / C5 x 128 draws per step):
-    // 16384: 168 ms / 14.0 s, 8192: 100 ms / 7.7 s, 4096: 73 ms / 4.82 s, 2048: 64 ms / 4.32 s, 1024: 65 ms / 4.45 s,
-    // 512: 65 ms / 4.59 s.  (More points per workgroup instead: the loop costs 32 VGPRs and two waves of occupancy, 78 ms.)
-    // (round 4, workgroups of 1024 points -- the C4 batch build -- share an index among four times the points: 3072 rows, 46.3 ms against
-    //  47.1 for C4 x 32; 4096: 46.5, 1024: 47.7.  C5 x 128 at 256 points per workgroup: 2048 rows 3.31 s, 4096: 4.35 s, 1024: 3.39 s.)
-    const int sampled_rows = (GRID_BS >= 1024) ? EG_GRID_SAMPLED_ROWS * 3 / 2 : EG_GRID_SAMPLED_ROWS;
-    if (grid_sampled && !getenv("EGDST_GRID_LDS") && grid_lrows > sampled_rows) grid_lrows = sampled_rows;
-#ifdef EGDST_EMU
-    if (grid_lrows > 20480) grid_lrows = 20480;
-#endif
-    // several asset points per lane (k_grid_lds_n: a point starts its bracket search at its neighbour's bracket) when the batch
-    // has points to spare: a lane per point otherwise, so that small batches keep their parallelism
-    // -- measured on MI355X (tests/diag/gpu_grid_ppl.py) and OFF by default: C2 x 4096 194.4 ms against 184.8 with a lane per
-    // point, C4 x 32 52.6 against 51.5, C5 x 128 3.72 s either way (133 VGPRs, three waves per SIMD instead of six to eight: what
-    // the shorter searches save, the lost occupancy costs again; compiled for 64 VGPRs it spills 2.4 KB per lane: 5.1 s).
-#ifdef EGDST_WITH_GRID_PPL  // (diagnostic builds only, tests/diag/gpu_grid_ppl.py)
-    const bool grid_ppl = getenv("EGDST_GRID_PPL") ? atoi(getenv("EGDST_GRID_PPL")) != 0 : false;
-#endif
-#ifdef EGDST_EMU
-    const int env_bs = ENV_MAXBS;
-#else
-    // 512 threads: the sort, compaction and classification phases scale with the threads, and since the walk is cut into
-    // one segment per wave (run_walk) so does the walk: 8 segments (measured, C2 x 4096: 287 ms with 256 threads, 273 with 512)
-    int env_bs = getenv("EGDST_ENV_256") ? 256 : ENV_MAXBS;
-    if (getenv("EGDST_ENV_BS")) env_bs = atoi(getenv("EGDST_ENV_BS"));  // experiments: 64, 128, 256, 512
-#endif
+    const int G = (h->opt.debug_sync || h->opt.debug_poison) ? 1 : h->nlanes;
     HIPCHK(hipMemsetAsync(b.work, 0, sizeof(unsigned) * g.ndraw, s));
     HIPCHK(hipMemsetAsync(b.nregen, 0, sizeof(unsigned) * g.ndraw, s));
     if (b.kcnt) HIPCHK(hipMemsetAsync(b.kcnt, 0, sizeof(int) * (size_t)g.nt * g.ndraw * MS_NST, s));
@@ -737,19 +916,13 @@ static int enqueue_solve(egdst_handle *h)
     HIPCHK(hipMemsetAsync(b.e1tiles, 0, sizeof(Env1Tile) * (size_t)g.ndraw * MS_NST * EG_E1_NB(g.ngridm), s));
     HIPCHK(hipMemsetAsync(b.e1done, 0, sizeof(unsigned) * (size_t)g.ndraw * MS_NST, s));
 #endif
-    // tables that may not fit the LDS whole: the sampled form of k_grid_lds needs to know that their M columns are in order
-    // (k_sortcheck), and with that knowledge the expectations of k_probe / k_fixup need one bracket search instead of two
-    const bool sortcheck = !grid_wide && grid_lrows > 0 && grid_sampled && g.nt < 4095;  // (the stamps hold the period in 12 bits)
     h->solve_seq++;
-    // whole tables (M, C, V) in LDS when they fit 48 KB (k_grid_lds_cv)
-    const bool grid_cv = !grid_sampled && grid_lrows > 0 && 24 * (long)grid_lrows <= 48 * 1024 &&
-                         (getenv("EGDST_GRID_CV") ? atoi(getenv("EGDST_GRID_CV")) != 0 : EG_GRID_CV_DEFAULT != 0);
     {   // the Batch every group's kernels read (constant address space), one copy per group with its schedule range
         for (int gi = 0; gi < G; gi++) {
             h->b_host[gi] = b;
             h->b_host[gi].draw0 = (G > 1) ? h->gstart[gi] : 0;
             h->b_host[gi].gdraws = ((G > 1) ? h->gstart[gi + 1] : g.ndraw) - h->b_host[gi].draw0;
-            h->b_host[gi].sorted_valid = sortcheck ? (int)((h->solve_seq & 0x3ffffu) << 12) + 1 : 0;
+            h->b_host[gi].sorted_valid = p.sortcheck ? (int)((h->solve_seq & 0x3ffffu) << 12) + 1 : 0;
         }
         HIPCHK(hipMemcpyAsync(h->b_dev, h->b_host, sizeof(Batch) * G, hipMemcpyHostToDevice, s));
     }
@@ -757,256 +930,50 @@ static int enqueue_solve(egdst_handle *h)
         HIPCHK(hipEventRecord(h->fork_ev, s));
         for (int gi = 0; gi < G; gi++) HIPCHK(hipStreamWaitEvent(h->gstream[gi], h->fork_ev, 0));
     }
-    // profiling: class k in {0 probe/terminal, 1 the grid kernel, 2 k_envelope, 3 regeneration (k_fixup_scan + k_fixup), and the
-    // kernels of the envelope step's throughput path: 4 k_tp_prep, 5 / 6 k_tp_sort stage 0 / 1, 7 / 8 k_tp_walk stage 0 / 1};
-    // events on the stream the kernels are launched on
-#define EG_EV(k, which) h->ev[(((size_t)gi * EG_NPROF + (k)) * g.nt + it) * 2 + (which)]
-    // (events are created when first recorded: a handle uses a fraction of the groups x classes x periods x 2 slots, and the
-    //  runtime's pool of timed events is finite -- 46 080 of them at once failed with "invalid resource handle")
-#define EG_REC(k, which, st)                                    \
-    do {                                                        \
-        if (h->profile) {                                       \
-            hipEvent_t &e_ = EG_EV(k, which);                   \
-            if (!e_) (void)hipEventCreate(&e_);                 \
-            if (e_) (void)hipEventRecord(e_, st);               \
-        }                                                       \
-    } while (0)
-#define EG_BEFORE(k) EG_REC(k, 0, gs)
-#define EG_END(k) EG_REC(k, 1, gs)
-#define EG_AFTER(name)                                                                  \
-    do {                                                                                \
-        if (dbgsync) {                                                                  \
-            hipError_t e_ = hipStreamSynchronize(gs);                                   \
-            fprintf(stderr, "[egdst] %s it=%d -> %s\n", name, it, hipGetErrorString(e_)); \
-            fflush(stderr);                                                             \
-        }                                                                               \
-    } while (0)
-#if MS_ND == 1
-    const bool env_tp = false;  // (the throughput path is for models with several choices)
-    // single-choice models: the regular cells are compacted by many workgroups (k_env1_*), k_envelope takes the rest
-    const int e1_nb = (int)EG_E1_NB(g.ngridm);
-    const bool e1_on = !getenv("EGDST_NO_ENV1");
-    const int e1_defer_all = getenv("EGDST_E1_DEFER_ALL") ? (atoi(getenv("EGDST_E1_DEFER_ALL")) == 2 ? 2 : 1) : 0;
-#define EG_ENVELOPE(terminal)                                                                                      \
-    do {                                                                                                          \
-        if (e1_on) {                                                                                              \
-            const size_t nc_ = (size_t)gdraws * MS_NST;                                                           \
-            hipLaunchKernelGGL(k_env1, dim3(e1_nb, (unsigned)nc_), dim3(E1_BS), 0, gs, bg, it, terminal, b.e1tiles, b.e1done, e1_nb, \
-                               (unsigned)(it + 1), e1_defer_all);                                                 \
-            hipLaunchKernelGGL(k_envelope, dim3(gdraws * MS_NST), dim3(env_bs), h->lds_bytes, gs, bg, it, terminal, \
-                               h->lcap, 1, 0, (const int *)nullptr, (const int *)nullptr);                                                                    \
-        } else                                                                                                    \
-            hipLaunchKernelGGL(k_envelope, dim3(gdraws * MS_NST), dim3(env_bs), h->lds_bytes, gs, bg, it, terminal, \
-                               h->lcap, 2, 0, (const int *)nullptr, (const int *)nullptr);                                                                    \
-    } while (0)
-#else
-    // several choices: the choice lists and their secondary envelopes as workgroups of their own (part 1), then the primary
-    // envelope per cell (part 2); one workgroup per cell (part 0) when the kink log is on (its rows are ordered) or on request
-    // -- for batches that leave CUs idle (measured: C3 single solve 42 -> 25 ms; C2 x 4096 274 -> 300 ms, where a workgroup
-    // that only compacts a list still takes a CU's LDS)
-    const bool env_parts = !h->two_pass && !b.klog &&
-                           (getenv("EGDST_ENV_PARTS") ? atoi(getenv("EGDST_ENV_PARTS")) != 0 : g.ndraw * MS_NST <= EG_ENV_WIDE_MAX_CELLS);
-    // Batches with many cells per period: the throughput path (k_tp_*: five lean kernels, one wave per walk, streams in global
-    // memory) does the regular cells, k_envelope (pass 1) the cells it left flagged in b.defer.  Not for the terminal period
-    // (one of nt), not with the kink log (its rows are ordered per cell), not for streams that a single wave should not walk
-    // alone (C5: 65 536 points per stream and few cells -- there the segmented walk of k_envelope is the right tool).
-    // points of a stream the kernels keep in LDS, per stage: a folded choice list with its extrapolation points (stage 0), the
-    // lists of all choices (stage 1); the kinks of the envelopes add a few rows each.  Longer streams -- degenerate guess
-    // streams -- are left to k_envelope.  (LDS per workgroup decides how many walks share a CU: measured on C2 x 4096,
-    // 2100 entries 201.7 ms, 2314: 209.8 ms, 3000: 225 ms.)
-    const long tp_keys = (long)MS_ND * g.ngridm + (long)g.ngridm / 10 + 64;
-    const long tp_keys0 = (long)g.ngridm + (long)g.ngridm / 8 + 64;
-    // EGDST_TP_LONG=1: streams too long for the walk's LDS by design (C5: 65 536 points, C3: 12 000) take the path too: the
-    // sorts work on a sampled index of the keys and the walks on global memory (k_tp_walk_g).  Bit-exact, and not the default:
-    // measured C5 x 128 3.89 s against 3.75 s, C3 x 64 51.5 against 37.7 ms, C5 x 16 720 against 763 ms (these batches are bound
-    // by k_grid_lds, which the envelope kernels already overlap with)
-    // (2: whatever the length of the streams -- tests)
-#ifdef EGDST_WITH_TP_LONG  // (diagnostic builds only, tests/diag/gpu_tp_long.py)
-    const int tp_long_ = getenv("EGDST_TP_LONG") ? atoi(getenv("EGDST_TP_LONG")) : 0;
-#else
-    const int tp_long_ = 0;
-#endif
-    const bool tp_long = tp_long_ == 2 || (tp_long_ == 1 && tp_keys > EG_ENV_TP_MAX_KEYS);
-    const bool env_tp = !h->two_pass && !b.klog &&
-                        (getenv("EGDST_ENV_TP") ? atoi(getenv("EGDST_ENV_TP")) != 0
-                                                : ((long)g.ndraw * MS_NST >= EG_ENV_TP_MIN_CELLS && (tp_long || tp_keys <= EG_ENV_TP_MAX_KEYS)));
-    int tp_lkcap = (int)(tp_keys < EG_ENV_TP_MAX_KEYS ? tp_keys : EG_ENV_TP_MAX_KEYS);
-#if !defined(EGDST_EMU) && MS_ND > 1
-    {   // three walks per CU where a slightly smaller stream budget buys that (C2: 2164 -> ~2060 points, streams hold ~2010)
-        hipFuncAttributes fa;
-        if (hipFuncGetAttributes(&fa, (const void *)k_tp_walk) == hipSuccess) {
-            const long cap3 = ((long)160 * 1024 / 3 - (long)fa.sharedSizeBytes - 512) / EG_TP_WALK_LDS_PER_POINT;
-            if (tp_lkcap > cap3 && cap3 >= (long)MS_ND * g.ngridm + 24) tp_lkcap = (int)cap3;
-        }
-    }
-#endif
-#ifdef EGDST_EMU
-    if (tp_lkcap > 6500) tp_lkcap = 6500;  // (the harness' static stand-in for the dynamic LDS, with its poisoned gaps)
-#endif
-    if (getenv("EGDST_TP_LKCAP")) tp_lkcap = atoi(getenv("EGDST_TP_LKCAP"));  // tests: a small value exercises the sampled key index
-    int tp_lkcap0 = (int)(tp_keys0 < tp_lkcap ? tp_keys0 : tp_lkcap);
-    if (getenv("EGDST_TP_LKCAP0")) tp_lkcap0 = atoi(getenv("EGDST_TP_LKCAP0"));
-    // tests: so few keys that the sorts work on a sampled index of them and write the permutation through global memory
-    const int tp_skcap = getenv("EGDST_TP_SORT_LKCAP") ? atoi(getenv("EGDST_TP_SORT_LKCAP")) : (tp_long ? EG_ENV_TP_LONG_KEYS : 0);
-    const int tp_scap0 = tp_skcap ? tp_skcap : tp_lkcap0, tp_scap1 = tp_skcap ? tp_skcap : tp_lkcap;
-    // threads of a walk workgroup per stage (all load the stream, its waves walk segments of it): experiments
-    int tp_walk_bs0 = getenv("EGDST_TP_WALK_BS0") ? atoi(getenv("EGDST_TP_WALK_BS0")) : EG_TP_WALK_BS0;
-    int tp_walk_bs1 = getenv("EGDST_TP_WALK_BS1") ? atoi(getenv("EGDST_TP_WALK_BS1")) : TP_WALK_BS;
-    if (tp_walk_bs0 < WAVE || tp_walk_bs0 > TP_WALK_BS || tp_walk_bs0 % WAVE) tp_walk_bs0 = TP_WALK_BS;
-    if (tp_walk_bs1 < WAVE || tp_walk_bs1 > TP_WALK_BS || tp_walk_bs1 % WAVE) tp_walk_bs1 = TP_WALK_BS;
-    const int tp_rest_grid = getenv("EGDST_TP_REST_GRID") ? atoi(getenv("EGDST_TP_REST_GRID")) : EG_ENV_TP_REST_GRID;
-    const int tp_big_grid = getenv("EGDST_TP_BIG_GRID") ? atoi(getenv("EGDST_TP_BIG_GRID")) : EG_ENV_TP_BIG_GRID;
-    // second tier of stage 1: lists beyond the regular stream budget that still fit the largest one (EGDST_TP_BIG=0: off, such
-    // cells are k_envelope's as in round 3)
-    int tp_bigcap = (int)(tp_keys * 2 < EG_ENV_TP_MAX_KEYS ? tp_keys * 2 : EG_ENV_TP_MAX_KEYS);
-#ifdef EGDST_EMU
-    if (tp_bigcap > 6500) tp_bigcap = 6500;
-#endif
-    if (getenv("EGDST_TP_BIGCAP")) tp_bigcap = atoi(getenv("EGDST_TP_BIGCAP"));
-    if (tp_bigcap > EG_ENV_TP_MAX_KEYS) tp_bigcap = EG_ENV_TP_MAX_KEYS;  // (what the kernels' dynamic LDS is reserved for)
-    const bool tp_big = !tp_long && !tp_skcap && tp_bigcap > tp_lkcap && tp_bigcap < 65536 && (getenv("EGDST_TP_BIG") ? atoi(getenv("EGDST_TP_BIG")) != 0 : true);
-    // (Measured and removed in round 4: a SLOW LANE per group -- the cells whose guess streams k_fixup has to regenerate, 3 % of the
-    //  cells of a C2 a0 = -5 period and 57 of the 172 ms of every group's chain (the regeneration itself, and the secondary envelope of a
-    //  re-based stream: a dozen nearly coincident pieces, the slowest of a launch's 270 walks at 0.4 ms against a mean of 42 us), taken
-    //  out of the period's launches and done by list-driven launches on a second stream of the group, the two meeting only before the
-    //  period's last kernel.  Bit-exact, and 348 ms per solve against 168 with 16 groups, 224 with 10, 237 with 8: two cross-stream event
-    //  dependencies per group and period (1 900 per solve) cost far more on this runtime than the overlap returns -- the same finding as
-    //  round 3's side stream for k_fixup alone.)
-    auto tp_sort_lds = [](int cap) {  // keys, class words, and the permutation at the next power of two (k_tp_sort)
-        int p2 = 1;
-        while (p2 < cap) p2 <<= 1;
-        return (size_t)12 * cap + (size_t)2 * p2 + 64;
-    };
-#ifdef EGDST_WITH_TP_LONG
-#define EG_TP_WALK_LONG(n, stage) if (tp_long) hipLaunchKernelGGL(k_tp_walk_g, dim3(n), dim3(TP_WALKG_BS), 0, gs, bg, it, stage, tlist_, tcnt_); else
-#else
-#define EG_TP_WALK_LONG(n, stage)
-#endif
-#define EG_ENVELOPE(terminal)                                                                                      \
-    do {                                                                                                          \
-        if (env_tp && !(terminal)) {                                                                              \
-            const unsigned nc_ = (unsigned)(gdraws * MS_NST);                                                     \
-            int *tcnt_ = b.tpn + (size_t)gi * g.nt + it, *tlist_ = b.tplist + (size_t)bg_draw0 * MS_NST;          \
-            int *bigc_ = b.tpbign + (size_t)gi * g.nt + it, *bigl_ = b.tpbiglist + (size_t)bg_draw0 * MS_NST;    \
-            EG_BEFORE(4);                                                                                         \
-            hipLaunchKernelGGL(k_tp_prep, dim3(nc_ * MS_ND), dim3(TP_BS), 0, gs, bg, it);                         \
-            if (dbl & 4) hipLaunchKernelGGL(k_tp_prep, dim3(nc_ * MS_ND), dim3(TP_BS), 0, gs, bg, it);            \
-            EG_END(4);                                                                                            \
-            EG_BEFORE(5);                                                                                         \
-            hipLaunchKernelGGL(k_tp_sort, dim3(nc_ * MS_ND), dim3(TP_SORT_BS), tp_sort_lds(tp_scap0), gs, bg, it, 0, tp_scap0, tp_long ? 0 : tp_lkcap0, 0, (int *)nullptr, (int *)nullptr); \
-            if (dbl & 8) hipLaunchKernelGGL(k_tp_sort, dim3(nc_ * MS_ND), dim3(TP_SORT_BS), tp_sort_lds(tp_scap0), gs, bg, it, 0, tp_scap0, tp_long ? 0 : tp_lkcap0, 0, (int *)nullptr, (int *)nullptr); \
-            EG_END(5);                                                                                            \
-            EG_BEFORE(7);                                                                                         \
-            EG_TP_WALK_LONG(nc_ * MS_ND, 0)                                                                        \
-                hipLaunchKernelGGL(k_tp_walk, dim3(nc_ * MS_ND), dim3(tp_walk_bs0), (size_t)EG_TP_WALK_LDS_PER_POINT * tp_lkcap0, gs, bg, it, 0, tlist_, tcnt_, tp_lkcap0); \
-            EG_END(7);                                                                                            \
-            EG_BEFORE(6);                                                                                         \
-            hipLaunchKernelGGL(k_tp_sort, dim3(nc_), dim3(TP_SORT_BS), tp_sort_lds(tp_scap1), gs, bg, it, 1, tp_scap1, tp_long ? 0 : tp_lkcap, \
-                               tp_big ? tp_bigcap : 0, tp_big ? bigl_ : (int *)nullptr, tp_big ? bigc_ : (int *)nullptr);  \
-            if (dbl & 16) hipLaunchKernelGGL(k_tp_sort, dim3(nc_), dim3(TP_SORT_BS), tp_sort_lds(tp_scap1), gs, bg, it, 1, tp_scap1, tp_long ? 0 : tp_lkcap, \
-                               0, (int *)nullptr, (int *)nullptr);                                                \
-            EG_END(6);                                                                                            \
-            EG_BEFORE(8);                                                                                         \
-            EG_TP_WALK_LONG(nc_, 1)                                                                                \
-                hipLaunchKernelGGL(k_tp_walk, dim3(nc_), dim3(tp_walk_bs1), (size_t)EG_TP_WALK_LDS_PER_POINT * tp_lkcap, gs, bg, it, 1, tlist_, tcnt_, tp_lkcap); \
-            if (tp_big) {                                                                                         \
-                const unsigned ng_ = nc_ < (unsigned)tp_big_grid ? nc_ : (unsigned)tp_big_grid;                    \
-                const size_t lds_ = tp_sort_lds(tp_bigcap) > (size_t)EG_TP_WALK_LDS_PER_POINT * tp_bigcap ? tp_sort_lds(tp_bigcap) : (size_t)EG_TP_WALK_LDS_PER_POINT * tp_bigcap; \
-                hipLaunchKernelGGL(k_tp_big, dim3(ng_), dim3(TP_SORT_BS), lds_, gs, bg, it, tlist_, tcnt_, tp_bigcap, (const int *)bigl_, (const int *)bigc_); \
-            }                                                                                                     \
-            EG_END(8);                                                                                            \
-            EG_BEFORE(2);                                                                                         \
-            hipLaunchKernelGGL(k_envelope, dim3(nc_ < (unsigned)tp_rest_grid ? nc_ : (unsigned)tp_rest_grid), dim3(env_bs), h->lds_bytes, gs, bg, it, \
-                               terminal, h->lcap, 3, 0, (const int *)tlist_, (const int *)tcnt_);                  \
-            EG_END(2);                                                                                            \
-        } else if (h->two_pass) {                                                                                 \
-            hipLaunchKernelGGL(k_envelope, dim3(gdraws * MS_NST), dim3(env_bs), (size_t)h->lcap_small * 32, gs, bg, it, \
-                               terminal, h->lcap_small, 0, 0, (const int *)nullptr, (const int *)nullptr);                                                    \
-            hipLaunchKernelGGL(k_envelope, dim3(gdraws * MS_NST), dim3(env_bs), h->lds_bytes, gs, bg, it, terminal, \
-                               h->lcap, 1, 0, (const int *)nullptr, (const int *)nullptr);                                                                    \
-        } else if (env_parts) {                                                                                   \
-            hipLaunchKernelGGL(k_envelope, dim3(gdraws * MS_NST * MS_ND), dim3(env_bs), h->lds_bytes, gs, bg, it, terminal, \
-                               h->lcap, 2, 1, (const int *)nullptr, (const int *)nullptr);                                                                    \
-            hipLaunchKernelGGL(k_envelope, dim3(gdraws * MS_NST), dim3(env_bs), h->lds_bytes, gs, bg, it, terminal, \
-                               h->lcap, 2, 2, (const int *)nullptr, (const int *)nullptr);                                                                    \
-        } else                                                                                                    \
-            hipLaunchKernelGGL(k_envelope, dim3(gdraws * MS_NST), dim3(env_bs), h->lds_bytes, gs, bg, it, terminal, \
-                               h->lcap, 2, 0, (const int *)nullptr, (const int *)nullptr);                                                                    \
-    } while (0)
-#endif
+    // the kink log (egdst_set_dbgout, which may be called after create) orders its rows per cell: one workgroup per cell
+    const bool env_tp = p.env_tp && !b.klog, env_parts = p.env_parts && !b.klog;
     // (Measured and not kept, r03: k_fixup on a side stream per group -- k_fixup_scan leaving the cells of a draw with a stream to
     //  regenerate to k_envelope's list pass, which then waits for the side stream -- so that the half millisecond of a
     //  regeneration is off the group's chain of dependent launches.  Bit-exact, and slower: 190-210 ms against 167 for C2 x 4096
     //  with 10-16 side streams on 24 hardware queues; the regeneration then took 1.1-1.7 ms from scan to done instead of 0.5.)
     for (int it = g.nt - 1; it >= 0; it--) {
-        if (poison) HIPCHK(hipMemsetAsync(h->scratch_lo, 0xAB, (size_t)(h->scratch_hi - h->scratch_lo), s));
+        if (h->opt.debug_poison) HIPCHK(hipMemsetAsync(h->scratch_lo, 0xAB, (size_t)(h->scratch_hi - h->scratch_lo), s));
         for (int gi = 0; gi < G; gi++) {
-            hipStream_t gs = (G > 1) ? h->gstream[gi] : s;
-            const Batch *const bg = h->b_dev + gi;   // (uploaded above: this group's draw0)
-            const int bg_draw0 = (G > 1) ? h->gstart[gi] : 0;
-            const int gdraws = ((G > 1) ? h->gstart[gi + 1] : g.ndraw) - bg_draw0;
+            const int draw0 = (G > 1) ? h->gstart[gi] : 0;
+            const int gdraws = ((G > 1) ? h->gstart[gi + 1] : g.ndraw) - draw0;
             if (gdraws <= 0) continue;
+            const GroupStep st = {h, gi, it, (G > 1) ? h->gstream[gi] : s, h->b_dev + gi, draw0, gdraws};  // (b_dev: uploaded above)
             const int combos = gdraws * MS_NST * MS_ND;
             if (it == g.nt - 1) {
-                dim3 grid((g.ngridm + GRID_BS - 1) / GRID_BS, combos);
-                EG_BEFORE(0);
-                hipLaunchKernelGGL(k_terminal, grid, dim3(GRID_BS), 0, gs, bg, it);
-                EG_END(0);
-                EG_AFTER("k_terminal");
-                EG_BEFORE(2);
-                EG_ENVELOPE(1);
-                EG_END(2);
-                EG_AFTER("k_envelope(T)");
-            } else {
-                if (sortcheck)
-                    hipLaunchKernelGGL(k_sortcheck, dim3((unsigned)((g.Sp + SORTCHK_ROWS - 1) / SORTCHK_ROWS), gdraws * MS_NST), dim3(GRID_BS), 0, gs,
-                                       bg, it);
-                EG_BEFORE(0);
-                hipLaunchKernelGGL(k_probe, dim3(combos), dim3(WAVE), 0, gs, bg, it);
-                if (dbl & 1) hipLaunchKernelGGL(k_probe, dim3(combos), dim3(WAVE), 0, gs, bg, it);
-                EG_END(0);
-                EG_AFTER("k_probe");
-                dim3 grid((g.ngridm - 1 + GRID_BS - 1) / GRID_BS, combos);
-                EG_BEFORE(1);
-                if (grid_wide) {
-                    dim3 gw(((g.ngridm - 1) * EG_GW + EG_GRIDW_BS - 1) / EG_GRIDW_BS, combos);
-                    hipLaunchKernelGGL(k_grid_wide, gw, dim3(EG_GRIDW_BS), 0, gs, bg, it);
-#ifdef EGDST_WITH_GRID_PPL
-                } else if (grid_lrows > 0 && grid_ppl) {
-                    dim3 gn((g.ngridm - 1 + GRID_BS * GRID_PPL - 1) / (GRID_BS * GRID_PPL), combos);
-                    hipLaunchKernelGGL(k_grid_lds_n, gn, dim3(GRID_BS), sizeof(double) * (size_t)grid_lrows, gs, bg, it, grid_lrows);
-#endif
-                } else if (grid_lrows > 0 && grid_cv) {
-                    hipLaunchKernelGGL(k_grid_lds_cv, grid, dim3(GRID_BS), 3 * sizeof(double) * (size_t)grid_lrows, gs, bg, it, grid_lrows);
-                    if (dbl & 2) hipLaunchKernelGGL(k_grid_lds_cv, grid, dim3(GRID_BS), 3 * sizeof(double) * (size_t)grid_lrows, gs, bg, it, grid_lrows);
-                } else if (grid_lrows > 0) {
-                    hipLaunchKernelGGL(k_grid_lds, grid, dim3(GRID_BS), sizeof(double) * (size_t)grid_lrows, gs, bg, it, grid_lrows);
-                }
-                else
-                    hipLaunchKernelGGL(k_grid, grid, dim3(GRID_BS), 0, gs, bg, it);
-                EG_END(1);
-                EG_BEFORE(3);
-                {
-                    int *cnt = b.fixn + (size_t)gi * g.nt + it, *list = b.fixlist + (size_t)bg_draw0 * MS_NST * MS_ND;
-                    hipLaunchKernelGGL(k_fixup_scan, dim3(combos), dim3(WAVE), 0, gs, bg, it, cnt, list);
-                    hipLaunchKernelGGL(k_fixup, dim3(combos < fix_grid ? combos : fix_grid), dim3(FIX_BS), 0, gs, bg, it,
-                                       (const int *)cnt, (const int *)list);
-                }
-                EG_END(3);
-                EG_AFTER("k_grid+k_fixup");
-                if (!env_tp) EG_BEFORE(2);   // (the throughput path brackets its kernels one by one)
-                EG_ENVELOPE(0);
-                if (!env_tp) EG_END(2);
-                EG_AFTER("k_envelope");
+                eg_before(st, 0);
+                hipLaunchKernelGGL(k_terminal, dim3((g.ngridm + GRID_BS - 1) / GRID_BS, combos), dim3(GRID_BS), 0, st.gs, st.bg, it);
+                eg_end(st, 0);
+                eg_after(st, "k_terminal");
+                enqueue_envelope(st, 1, env_tp, env_parts);
+                eg_after(st, "k_envelope(T)");
+                continue;
             }
+            if (p.sortcheck)
+                hipLaunchKernelGGL(k_sortcheck, dim3((unsigned)((g.Sp + SORTCHK_ROWS - 1) / SORTCHK_ROWS), gdraws * MS_NST), dim3(GRID_BS), 0,
+                                   st.gs, st.bg, it);
+            eg_before(st, 0);
+            hipLaunchKernelGGL(k_probe, dim3(combos), dim3(WAVE), 0, st.gs, st.bg, it);
+            eg_end(st, 0);
+            eg_after(st, "k_probe");
+            eg_before(st, 1);
+            enqueue_grid(st, combos);
+            eg_end(st, 1);
+            eg_before(st, 3);
+            int *cnt = b.fixn + (size_t)gi * g.nt + it, *list = b.fixlist + (size_t)draw0 * MS_NST * MS_ND;
+            hipLaunchKernelGGL(k_fixup_scan, dim3(combos), dim3(WAVE), 0, st.gs, st.bg, it, cnt, list);
+            hipLaunchKernelGGL(k_fixup, dim3(combos < EG_FIX_GRID ? combos : EG_FIX_GRID), dim3(FIX_BS), 0, st.gs, st.bg, it, (const int *)cnt,
+                               (const int *)list);
+            eg_end(st, 3);
+            eg_after(st, "k_grid+k_fixup");
+            enqueue_envelope(st, 0, env_tp, env_parts);
+            eg_after(st, "k_envelope");
         }
     }
-#undef EG_AFTER
-#undef EG_BEFORE
-#undef EG_END
-#undef EG_REC
-#undef EG_EV
-#undef EG_ENVELOPE
     if (G > 1)  // join: the handle's stream continues when every group is done
         for (int gi = 0; gi < G; gi++) {
             HIPCHK(hipEventRecord(h->join_ev[gi], h->gstream[gi]));
@@ -1016,6 +983,13 @@ static int enqueue_solve(egdst_handle *h)
     h->solved = 1;
     if (h->imported) memset(h->imported, 0, (size_t)g.ndraw);
     return 0;
+}
+
+extern "C" int egdst_solve_async(egdst_handle *h)
+{
+    if (!h) return set_err(EGDST_E_ARG, "null handle");
+    if (!h->params_set && MS_NPARAM) return set_err(EGDST_E_ARG, "egdst_solve: parameters not set");
+    return enqueue_solve(h);
 }
 
 extern "C" int egdst_sync(egdst_handle *h)
@@ -1716,10 +1690,6 @@ extern "C" int egdst_set_dbgout(egdst_handle *h, int on)
         if (b.klog) (void)hipFree(b.klog);
         if (b.kcnt) (void)hipFree(b.kcnt);
         b.klog = nullptr, b.kcnt = nullptr, b.kcap = 0;
-        if (h->graph_exec) {  // (a captured launch sequence holds the old kernel arguments: the freed log)
-            (void)hipGraphExecDestroy(h->graph_exec);
-            h->graph_exec = nullptr;
-        }
         return 0;
     }
     if (b.klog) return 0;
@@ -1736,10 +1706,6 @@ extern "C" int egdst_set_dbgout(egdst_handle *h, int on)
     }
     b.kcap = (int)cap;
     HIPCHK(hipMemsetAsync(b.kcnt, 0, sizeof(int) * cells, h->stream));
-    if (h->graph_exec) {  // (a captured launch sequence holds the old kernel arguments)
-        (void)hipGraphExecDestroy(h->graph_exec);
-        h->graph_exec = nullptr;
-    }
     return 0;
 }
 

@@ -1594,9 +1594,6 @@ template <int PPL, bool CV = false> static __device__ __forceinline__ void eg_gr
     }
 }
 
-#ifndef GRID_PPL
-#define GRID_PPL 4  // asset points per lane of k_grid_lds_n (the form for batches with points to spare)
-#endif
 __global__ void __launch_bounds__(GRID_BS, GRID_MINW) k_grid_lds(const Batch *bp_, int it, int lrows)
 {
     eg_grid_lds_body<1>(EG_BATCH_REF(bp_), it, lrows);
@@ -1607,15 +1604,6 @@ __global__ void __launch_bounds__(GRID_BS, GRID_MINW) k_grid_lds_cv(const Batch 
 {
     eg_grid_lds_body<1, true>(EG_BATCH_REF(bp_), it, lrows);
 }
-#ifdef EGDST_WITH_GRID_PPL  // diagnostic builds only (tests/diag/gpu_grid_ppl.py): measured not faster in round 3
-#ifndef GRID_N_MINW
-#define GRID_N_MINW 1  // (the lane's points side by side want registers: 133 VGPRs by default, three waves per SIMD)
-#endif
-__global__ void __launch_bounds__(GRID_BS, GRID_N_MINW) k_grid_lds_n(const Batch *bp_, int it, int lrows)
-{
-    eg_grid_lds_body<GRID_PPL>(EG_BATCH_REF(bp_), it, lrows);
-}
-#endif
 
 // k_grid for small batches: 16 lanes per grid point, a lane per shock node (eg_wave_expectation with groups of 16),
 // so that a solve that leaves the GPU mostly idle does not spend 20 serial shock terms per point: same arithmetic and
@@ -2923,6 +2911,9 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
 // pass 0: launched with a small lcap so that two workgroups share a CU; a cell whose stream does not fit is left
 //         untouched and flagged in b.defer;  pass 1: launched with the large lcap, works on the flagged cells only
 //         (streams beyond that sort and walk in global memory);  pass 2: every cell, one launch (no deferral).
+// (The host no longer launches pass 0: the two-launch mode was measured slower and removed.  Its branch stays, because
+//  without it the compiler allocates k_envelope's registers worse -- more SGPR spills in the default builds, more VGPR spills
+//  in the C2 batch build.)
 #ifndef ENV_MINW
 #define ENV_MINW 1
 #endif
@@ -3817,7 +3808,7 @@ __global__ void __launch_bounds__(TP_BS, TP_PREP_MINW) k_tp_prep(const Batch *bp
 // lkcap: M keys that fit the dynamic LDS.
 // bxi: stage 0: cell slot * MS_ND + choice; stage 1: cell slot
 // wcap: points the walk of this stage keeps in LDS -- a longer stream (a degenerate guess stream: thousands of repeated
-// points) is k_envelope's, and is not sorted here either; 0: no limit (the walks run on global memory, k_tp_walk_g)
+// points) is k_envelope's, and is not sorted here either; 0: no limit (no launch passes 0)
 // big (stage 1 only): the second tier of the stage -- the cells whose lists exceed the stream budget of the regular launch (wcap:
 // what lets three walks share a CU) but fit the largest one (bigcap) are flagged TP_BIG and listed (biglist, bigcnt) by the
 // regular launch and done by a second, small launch with the large budget (big != 0: bxi comes from that list).  On C2 with the
@@ -4201,18 +4192,6 @@ __global__ void __launch_bounds__(TP_SORT_BS, TP_WALK_MINW) k_tp_big(const Batch
         __syncthreads();  // (the LDS of the cell is reused by the next one)
     }
 }
-#ifdef EGDST_WITH_TP_LONG  // diagnostic builds only (tests/diag/gpu_tp_long.py): measured not faster than k_envelope's global walk in round 3
-#ifdef EGDST_EMU
-#define TP_WALKG_BS ENV_BS_EMU
-#else
-#define TP_WALKG_BS 512  // eight walking waves for the long streams
-#endif
-__global__ void __launch_bounds__(TP_WALKG_BS, TP_WALK_MINW) k_tp_walk_g(const Batch *bp_, int it, int stage, int *list, int *cnt)
-{
-    __shared__ TpShared S;
-    tp_walk<true>(EG_BATCH_REF(bp_), it, stage, list, cnt, 0, (int)blockIdx.x, &S, nullptr);
-}
-#endif
 
 // (Measured and not kept: the same phases FUSED into two kernels -- per (cell, choice) the list, its sort and its secondary
 //  envelope; per cell the sort of the lists and the primary envelope -- so that a launch costs the slowest chain of phases

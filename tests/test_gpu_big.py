@@ -146,7 +146,7 @@ def test_batch_build_variants_of_the_stress_configs_equal_the_fixtures(name, wl)
 
 
 def _solve_with_env(lib, m, P, env):
-    """a kept-history solve with environment switches of the library set for the duration of the solve (they are read at solve time)"""
+    """a kept-history solve with environment switches of the library set while its handle is created (they are read at create)"""
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:

@@ -272,7 +272,7 @@ def test_throughput_envelope_path_bit_exact(name, keys, monkeypatch):
     egdst_kernels.hip) and hands the cells it does not take to k_envelope.  Forced on here for single solves (EGDST_ENV_TP=1):
     tables, thresholds and evaluation counts equal the oracle's bit for bit, with the sort's M keys whole in LDS and with so
     little LDS that it works on a sampled index of them; and the path really does the cells (egdst_get_tp_stats).  (The walks over
-    global memory, k_tp_walk_g, were measured slower in round 3 and are compiled into diagnostic builds only since round 4.)"""
+    global memory, k_tp_walk_g, were measured slower in round 3 and have been removed.)"""
     monkeypatch.setenv('EGDST_ENV_TP', '1')
     if keys != 'lds_keys':
         monkeypatch.setenv('EGDST_TP_SORT_LKCAP', '96')
@@ -304,6 +304,8 @@ def test_throughput_envelope_path_in_a_batch_with_failing_draws(monkeypatch):
         if tp == '0':
             monkeypatch.setenv('EGDST_ENV_TP', '0')
         s = runtime.Solver(lib, m.descriptor(), ndraw=len(P), keep_history=True)
+        if tp == '0':
+            monkeypatch.delenv('EGDST_ENV_TP')   # (switches are read when the handle is created)
         s.set_params(P)
         s.solve(raise_on_error=False)
         res[tp] = (s.status(), s.evals()[1], s.objective(), [s.checksums(i) for i in range(0, len(P), 7)], s.tp_stats())
@@ -647,7 +649,7 @@ def test_branch_free_bracket_search_is_the_binary_search(name, monkeypatch):
     bxsearch_common lands (egdst_lib.c:136-166) -- and the two divisions of every interpolation share one refined reciprocal
     (eg_lerp_fast).  Tables, thresholds and evaluation counts equal the oracle's bit for bit, with whole columns in LDS and with
     the sampled index (the search is then finished in the window of the global column).  (The neighbour-hinted search this test
-    covered until round 3, k_grid_lds_n, was measured slower and is compiled into diagnostic builds only.)"""
+    covered until round 3, k_grid_lds_n, was measured slower and has been removed.)"""
     monkeypatch.setenv('EGDST_GRID_WIDE', '0')
     m = {'retirement2': lambda: examples.retirement2(), 'occ3_n400': SCALED['occ3_n400'], 'retire8': lambda: examples.retirement8(T=12, ngridm=150, ny=5),
          'C2': SCALED['C2'], 'deaton_n4096': SCALED['deaton_n4096'], 'cake_normal': lambda: examples.cake_normal()}[name]()
