@@ -17,6 +17,11 @@ it then meets (--no-perturb: the same draws every step).
 Draws are independent: no data-path collective; after the timed steps the per-draw objective
 contributions are reduced with one RCCL all-reduce.  Rank 0 prints ONE JSON line.
 
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the steps, writes --dump-outputs
+and prints the line (`value`, `ms_per_step`, the step counters, `config`).  --full adds everything below `value` here
+(`roofline` with its per-kernel profiles, `legs` / `strong`, `cpu_baseline`, the one-draw latencies, the copy rate); the
+--no-* options take parts of it out again.
+
 value       = evaluations EXECUTED for the draws that solved (failed draws and the evaluations the device credits
               without executing -- include/egdst.h egdst_get_evals_credited -- are left out), all ranks, all timed
               steps / max-over-ranks wall time.  `evals_reference_per_step` is what the reference would count.
@@ -398,7 +403,24 @@ def dump_outputs(path, objective, chunks, rank, world, limit=DUMP_LIMIT_BYTES):
         np.save(os.path.join(path, name + suffix + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
-def main():
+def extras(args, world):
+    """What a run measures beside its timed steps: {name: runs?}.  All off in a plain run; --full turns them on as far as the
+    configuration has them, and the --no-* options take them out again."""
+    full, one = args.full, args.full and world == 1
+    legs = (full and not args.no_legs and (not args.small or args.rehearse_legs) and args.workload == 'C2' and args.scaling == 'weak'
+            and args.rows_cap == 0)
+    return {'kernel_profile': full,                                   # kernel_ms_* and roofline: one more solve with HIP events
+            'one_group_profile': one and not args.no_extras,          # roofline.ceilings: one more solve with one draw group
+            'single_solve': one and not args.no_single_solve,
+            'single_solve_export': one and not args.no_single_solve and not args.no_extras,
+            'single_solve_other': one and not args.no_single_solve and not args.no_extras and args.workload == 'C2' and not args.small,
+            'copy_rate': one and not args.no_extras,
+            'legs': legs and world == 1,
+            'strong': legs and world > 1,
+            'cpu_baseline': one and not args.no_cpu_baseline}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
@@ -411,17 +433,24 @@ def main():
     ap.add_argument('--rows-cap', type=int, default=0, help='compact physical row capacity (0 = exact, ngridmax rows)')
     ap.add_argument('--small', action='store_true', help='reduced grid of the workload (plumbing rehearsals, not a result)')
     ap.add_argument('--no-perturb', action='store_true', help='the same draws every step')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-single-solve', action='store_true', help='skip the one-draw latency legs (profiling runs)')
-    ap.add_argument('--no-extras', action='store_true', help='skip the copy-peak, export and estimation legs')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also the per-kernel profiles and roofline, the legs, the CPU baseline, the one-draw '
+                         'latencies and the copy rate (see extras); a plain run measures its timed steps only')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-single-solve', action='store_true', help='--full without the one-draw latency legs (profiling runs)')
+    ap.add_argument('--no-extras', action='store_true', help='--full without the copy rate, the one-group profile, the export and the other one-draw latencies')
     ap.add_argument('--rehearse-legs', action='store_true', help='N > 1: the strong-scaling sub-records on reduced batches (C5 x 32, C4 x 8 draws): a plumbing rehearsal on one card, not a result')
-    ap.add_argument('--no-legs', action='store_true', help='skip the legs of the stress configurations (C4 x 32, C5 x 128, C2 a0=0; N > 1: the strong-scaling batches)')
+    ap.add_argument('--no-legs', action='store_true', help='--full without the legs of the stress configurations (C4 x 32, C5 x 128, C2 a0=0; N > 1: the strong-scaling batches)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step returned to its caller as DIR/<name>.npy (see dump_outputs)')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
 
@@ -458,9 +487,7 @@ def main():
     if args.small:
         wl_kw = {'C2': dict(ngridm=200, T=20), 'C4': dict(ngridm=2048, T=20), 'C5': dict(ngridm=500, T=20)}.get(args.workload, {})
     model, drawgen = workloads.WORKLOADS[args.workload](**wl_kw)
-    lib = build.build_model(model)  # prebuilt in-tree by __graft_entry__.build(); rebuilds if stale
     desc = model.descriptor()
-    nparam = lib.info.nparam
 
     # ---- the draws of this rank, per step ---------------------------------------------------------------------
     if args.scaling == 'weak':
@@ -474,6 +501,15 @@ def main():
     chunk = max(1, min(chunk, max(mine_n, 1)))
     plan = parallel.plan_chunks(mine_n, chunk)     # [(first draw of the shard, draws that count)] per chunk
     nsteps_all = args.warmup + args.steps
+    ex = extras(args, world)
+
+    # large batches of a workload may have a build variant of their own (workloads.BATCH_BUILD_FLAGS: other register
+    # budgets for k_envelope or k_grid_lds); the one-draw latency legs of --full use the default build, which a plain run
+    # then does not load.  Both are prebuilt in-tree by __graft_entry__.build() (rebuilt here if stale).
+    batch_flags = workloads.BATCH_BUILD_FLAGS.get(args.workload, []) if (chunk >= workloads.BATCH_BUILD_MIN_DRAWS.get(args.workload, 1 << 30) and not args.small) else []
+    lib = build.build_model(model) if (ex['single_solve'] or not batch_flags) else None
+    lib_batch = build.build_model(model, extra_flags=batch_flags) if batch_flags else lib
+    nparam = lib_batch.info.nparam
 
     def step_draws(s):
         """the job's draws, moved a little from step to step as an estimation loop would move them (each parameter times
@@ -495,10 +531,6 @@ def main():
             dev[s, :padded] = torch.from_numpy(pp).cuda()
 
     stream = torch.cuda.Stream()
-    # large batches of a workload may have a build variant of their own (workloads.BATCH_BUILD_FLAGS: other register
-    # budgets for k_envelope or k_grid_lds); the one-draw latency legs below use the default build
-    batch_flags = workloads.BATCH_BUILD_FLAGS.get(args.workload, []) if (chunk >= workloads.BATCH_BUILD_MIN_DRAWS.get(args.workload, 1 << 30) and not args.small) else []
-    lib_batch = build.build_model(model, extra_flags=batch_flags) if batch_flags else lib
     solver = runtime.Solver(lib_batch, desc, ndraw=chunk, keep_history=False, stream=stream.cuda_stream, rows_cap=args.rows_cap) if mine_n else None
     obj = torch.full((nsteps_all, max(padded, 1), 2), float('nan'), dtype=torch.float64, device='cuda')
     torch.cuda.synchronize()
@@ -553,11 +585,12 @@ def main():
     if args.dump_outputs and mine_n:
         dump_outputs(args.dump_outputs, obj[nsteps_all - 1, :mine_n].cpu().numpy(), last_chunks, rank, world)
 
-    # the last step's draws once more with HIP events around every launch (16 streams), then with one draw group: outside the timed region
-    kms, klaunch, algbytes = profiled_step(solver) if solver else (np.zeros(9), np.zeros(9, dtype=np.int32), 0)
-    tps_last = solver.tp_stats() if solver else np.zeros((1, 2))
-    regen_last = int(solver.regenerations().sum()) if solver else 0
-    serial_ms, serial_launch = serial_profile(solver) if (solver and rank == 0 and world == 1 and not args.no_extras) else (None, None)
+    if ex['kernel_profile']:
+        # the last step's draws once more with HIP events around every launch (16 streams), then with one draw group: outside the timed region
+        kms, klaunch, algbytes = profiled_step(solver) if solver else (np.zeros(9), np.zeros(9, dtype=np.int32), 0)
+        tps_last = solver.tp_stats() if solver else np.zeros((1, 2))
+        regen_last = int(solver.regenerations().sum()) if solver else 0
+        serial_ms, serial_launch = serial_profile(solver) if (solver and ex['one_group_profile']) else (None, None)
     # ---- final objective reduce: the only collective of the path (RCCL over xGMI when world > 1) -----------------
     last = obj[nsteps_all - 1, :mine_n, 0] if mine_n else torch.zeros(0, dtype=torch.float64, device='cuda')
     okmask = ~torch.isnan(last)
@@ -582,9 +615,8 @@ def main():
 
     # ---- N > 1: the north_star's batches, strong scaling -- one timed step of C5 x 1024 and of C4 x 256 draws sharded over the
     # ranks (contiguous shards, chunks that fit HBM through one handle, no collective but the timing barriers over gloo)
-    want_legs = not args.no_legs and (not args.small or args.rehearse_legs) and args.workload == 'C2' and args.scaling == 'weak' and args.rows_cap == 0
     strong = None
-    if want_legs and world > 1:
+    if ex['strong']:
         if solver:
             solver.close()
             solver = None
@@ -621,7 +653,7 @@ def main():
             'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
             'config': {'workload': '%s%s: %s, T=%d, ngridm=%d, ny=%d, nd=%d, nst=%d, a0=%g, mmax=%g' % (
                 args.workload, ' (REDUCED GRID, rehearsal only)' if args.small else '', model.label, desc['T'], desc['ngridm'],
-                desc['ny'], lib.info.nd, lib.info.nst, desc['a0'], desc['mmax']),
+                desc['ny'], lib_batch.info.nd, lib_batch.info.nst, desc['a0'], desc['mmax']),
                 'draws_per_step_all_gpus': job, 'draws_per_gpu': args.ndraw if args.scaling == 'weak' else '%d..%d' % (job // world, -(-job // world)),
                 'chunk_draws_per_handle': chunk, 'chunks_per_step_rank0': nchunks, 'rows_cap': args.rows_cap, 'batch_build_flags': batch_flags,
                 'draws_perturbed_every_step': not args.no_perturb,
@@ -631,15 +663,17 @@ def main():
             'step_ms_rank0': [round(t, 2) for t in step_ms],
             'capacity_retries': main_extra['capacity_retries'], 'schedule': main_extra['schedule'],
             'objective_mean': float(red[0].item() / max(red[1].item(), 1.0)),
-            'kernel_ms_last_solve_summed_over_concurrent_streams': {n: float(v) for n, v in zip(CLASS_NAMES, kms)},
             'envelope_cells_by_throughput_path': main_extra['envelope_cells_by_throughput_path'],
-            'roofline': roofline_record('%s_ndraw%d' % (args.workload, chunk), kms, klaunch, algbytes, ev_exec_all / args.steps / max(world * nchunks, 1),
-                                        ev_exec_all / dt_max, ms_step / max(nchunks, 1), chunk * lib.info.nst * (desc['T'] - desc['t0'] + 1),
-                                        int(tps_last[:, 1].sum()) if (lib.info.nd > 1 and int(tps_last.sum()) > 0) else chunk * lib.info.nst * (desc['T'] - desc['t0'] + 1),
-                                        regen_last, small=args.small, serial_ms=serial_ms, serial_launch=serial_launch),
+            'full': args.full,
         }
+        if ex['kernel_profile']:
+            out['kernel_ms_last_solve_summed_over_concurrent_streams'] = {n: float(v) for n, v in zip(CLASS_NAMES, kms)}
+            out['roofline'] = roofline_record('%s_ndraw%d' % (args.workload, chunk), kms, klaunch, algbytes, ev_exec_all / args.steps / max(world * nchunks, 1),
+                                              ev_exec_all / dt_max, ms_step / max(nchunks, 1), chunk * lib_batch.info.nst * (desc['T'] - desc['t0'] + 1),
+                                              int(tps_last[:, 1].sum()) if (lib_batch.info.nd > 1 and int(tps_last.sum()) > 0) else chunk * lib_batch.info.nst * (desc['T'] - desc['t0'] + 1),
+                                              regen_last, small=args.small, serial_ms=serial_ms, serial_launch=serial_launch)
         one = np.asarray(model.param_vector(), dtype=np.float64)[None] if mine_n else None   # fixed parameters: comparable from run to run
-        if not args.no_single_solve and world == 1 and mine_n:
+        if ex['single_solve'] and mine_n:
             # single-solve latency (one draw): the "full backward-induction wall time" half of the metric
             s1 = runtime.Solver(lib, desc, ndraw=1, keep_history=False)
             s1.set_params(one)
@@ -649,7 +683,7 @@ def main():
                 s1.solve(raise_on_error=False)
             out['single_solve_ms'] = (time.perf_counter() - t1) / 3 * 1e3
             s1.close()
-            if not args.no_extras:
+            if ex['single_solve_export']:
                 # the same including the D2H copy of the full solution (SURVEY.md section 8d metric 2)
                 s2 = runtime.Solver(lib, desc, ndraw=1, keep_history=True)
                 s2.set_params(one)
@@ -660,7 +694,7 @@ def main():
                 out['single_solve_plus_export_ms'] = (time.perf_counter() - t1) * 1e3
                 out['export_bytes'] = int(sol.len.sum()) * 24 + int(sol.thlen.sum()) * 16
                 s2.close()
-        if not args.no_extras and not args.no_single_solve and world == 1 and args.workload == 'C2' and not args.small:
+        if ex['single_solve_other']:
             # the other one-draw latencies the verdicts follow: C2 with a0 = 0 (the configuration of rounds 1-3) and C3
             def one_solve(mk):
                 mm = mk()
@@ -674,7 +708,7 @@ def main():
                 ss.close()
                 return r_
             out['single_solve_other'] = {'c2_a0_0': one_solve(lambda: workloads.c2(a0=0)[0]), 'c3': one_solve(lambda: workloads.c3()[0])}
-        if not args.no_extras and world == 1:
+        if ex['copy_rate']:
             # measured streaming-copy rate of this box (read + write), the practical HBM ceiling beside the 8 TB/s spec
             a = torch.empty(1 << 28, dtype=torch.float64, device='cuda')   # 2 GiB
             b_ = torch.empty_like(a)
@@ -688,7 +722,7 @@ def main():
             del a, b_
         if strong is not None:
             out['strong'] = strong
-        if want_legs and world == 1:
+        if ex['legs']:
             # the per-GPU shares of the stress configurations and C2 on the surveyed credit limit (see the module docstring)
             if solver:
                 solver.close()
@@ -704,7 +738,7 @@ def main():
             for v in legs.values():
                 v.pop('_raw', None)
             out['legs'] = legs
-        if not args.no_cpu_baseline and world == 1 and mine_n:   # reported baseline: rank 0 at N=1 only
+        if ex['cpu_baseline'] and mine_n:   # reported baseline: rank 0 at N=1 only
             out['cpu_baseline'] = cpu_baseline(args.workload, wl_kw, host_draws[-1])
             out['speedup_vs_cpu_1thread'] = out['value'] / out['cpu_baseline']['value']
             if out.get('single_solve_ms'):

@@ -16,7 +16,7 @@ p5="WRITE_SIZE"
 i=0
 for p in "$p1" "$p2" "$p3" "$p4" "$p5"; do
   i=$((i+1))
-  rocprofv3 --pmc $p --kernel-trace --output-format csv -d $out/pass$i -- python bench.py "$@" > $out/pass$i.json 2> $out/pass$i.err || { echo "pass $i failed"; tail -5 $out/pass$i.err; exit 1; }
+  rocprofv3 --pmc $p --kernel-trace --output-format csv -d $out/pass$i -- python bench.py --full "$@" > $out/pass$i.json 2> $out/pass$i.err || { echo "pass $i failed"; tail -5 $out/pass$i.err; exit 1; }
   echo "pass $i done"
 done
 python tools/pmc_summary.py $out > $out/summary.csv

@@ -8,7 +8,7 @@ tag=$1
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/$tag
 mkdir -p $out
-common="--no-cpu-baseline --no-single-solve --no-extras --no-legs"
+common="--full --no-cpu-baseline --no-single-solve --no-extras --no-legs"
 run() {  # name, env..., -- bench args
   name=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/$name -- python bench.py "$@" > $out/$name.json 2> $out/$name.err || { echo "$name failed"; tail -5 $out/$name.err; exit 1; }
