@@ -4853,6 +4853,98 @@ __global__ void k_moment_objective(const double *means, const int *counts, int n
     obj[d] = acc;
 }
 
+// One user-defined moment (egdst_moment, include/egdst.h) of one draw's simulated paths.  One workgroup per (moment, draw
+// of the slice); each thread adds the qualifying values of its agents in index order, within an agent in period order,
+// then the same fixed tree as k_moments: a kind-0 moment of one period without condition is exactly k_moments' cell.
+__global__ void __launch_bounds__(MOM_BS) k_moments_spec(const double *sims, int nsim, int nt, int nout, const egdst_moment *spec,
+                                                         int nmom, double *means, int *counts)
+{
+    __shared__ double ssum[MOM_BS];
+    __shared__ int scnt[MOM_BS];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const egdst_moment q = spec[j];
+    const size_t per_agent = (size_t)nout * nt;
+    sims += (size_t)blockIdx.y * per_agent * nsim;
+    means += (size_t)blockIdx.y * nmom;
+    counts += (size_t)blockIdx.y * nmom;
+    double acc = 0;
+    int cnt = 0;
+    for (int i = tid; i < nsim; i += MOM_BS) {
+        const double *p = sims + (size_t)i * per_agent;
+        for (int it = q.it_first; it <= q.it_last; it++) {
+            const double *o = p + (size_t)it * nout;
+            const double v = o[q.col];
+            if (!(v == v)) continue;
+            if (q.cond_col >= 0) {
+                const double c = o[q.cond_col];
+                if (!(c >= q.cond_lo && c <= q.cond_hi)) continue;   // (NaN fails both)
+            }
+            double x = v;
+            if (q.kind == 1) {
+                const double w = o[q.col2];
+                if (!(w == w)) continue;
+                x = v * w;
+            } else if (q.kind == 2) {
+                x = (v >= q.lo && v <= q.hi) ? 1.0 : 0.0;
+            }
+            acc += x, cnt++;
+        }
+    }
+    ssum[tid] = acc;
+    scnt[tid] = cnt;
+    __syncthreads();
+    for (int o = MOM_BS / 2; o > 0; o >>= 1) {
+        if (tid < o) ssum[tid] += ssum[tid + o], scnt[tid] += scnt[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        counts[j] = scnt[0];
+        means[j] = scnt[0] ? ssum[0] / scnt[0] : NAN;
+    }
+}
+
+// Quadratic form e' W e of one draw's moments, e = means - target, W [nmom x nmom] row-major: r_j = sum over the non-zero
+// W_jk in k order of W_jk * e_k, obj = sum over the rows with a non-zero entry in j order of e_j * r_j; NaN if a moment that
+// W touches (row or column) is empty.  One workgroup per draw: the threads form the terms e_j * r_j of MOM_BS rows at a time,
+// thread 0 adds them in row order (deterministic).  With a diagonal W this is k_moment_objective's w * e * e, bit for bit
+// (the products commute and +0 + x is x).
+__global__ void __launch_bounds__(MOM_BS) k_moment_objective_w(const double *means, const int *counts, int nmom,
+                                                               const double *target, const double *W, double *obj)
+{
+    __shared__ double sterm[MOM_BS];
+    __shared__ int sflag[MOM_BS];   // bit 0: the row has a non-zero entry, bit 1: it touches an empty moment
+    const int tid = threadIdx.x;
+    const double *m = means + (size_t)blockIdx.x * nmom;
+    const int *c = counts + (size_t)blockIdx.x * nmom;
+    double acc = 0;
+    int empty = 0;
+    for (int j0 = 0; j0 < nmom; j0 += MOM_BS) {
+        const int j = j0 + tid;
+        double term = 0;
+        int flag = 0;
+        if (j < nmom) {
+            const double *w = W + (size_t)j * nmom;
+            double r = 0;
+            for (int k = 0; k < nmom; k++) {
+                if (w[k] == 0.0) continue;
+                flag |= (c[j] == 0 || c[k] == 0) ? 3 : 1;
+                r += w[k] * (m[k] - target[k]);
+            }
+            term = (m[j] - target[j]) * r;
+        }
+        sterm[tid] = term;
+        sflag[tid] = flag;
+        __syncthreads();
+        if (tid == 0)
+            for (int t = 0; t < MOM_BS && j0 + t < nmom; t++) {
+                empty |= sflag[t] >> 1;
+                if (sflag[t]) acc += sterm[t];
+            }
+        __syncthreads();
+    }
+    if (tid == 0) obj[blockIdx.x] = empty ? NAN : acc;
+}
+
 // zero_first: the gateway's NaN fill starts at element 1 of its output array (egdst_simulator.c:105: element 0 is written by
 // agent 0 anyway, or stays 0.0); the batched estimation step (egdst_simulate_batch_moments) promises NaN moments for a draw
 // that failed or whose agent 0 has no value, so there every element is NaN

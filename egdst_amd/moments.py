@@ -1,0 +1,221 @@
+"""User-defined simulated moments for the estimation step (egdst_simulate_batch_spec, include/egdst.h).
+
+    from egdst_amd import moments as mo
+    spec = mo.MomentSpec([mo.share('id', k, periods=it) for it in range(nt) for k in range(3)]
+                         + [mo.mean('C', periods=(0, 9), where=('id', 2, 2)), mo.cross('M', 'C')], layout=solver.lib.info)
+    means, counts, obj = solver.simulate_batch_spec(init, spec, target=t, W=W)
+    data_means, data_counts = spec.evaluate(data_panel)      # the same definitions, summed in the same order, on the host
+
+Columns are 0-based indices of the simulated panel (egdst_simulate, model.sims) or the tokens of the model strings:
+M C A V id ist mu sigma shock u df, then st1.. (nnst states), dc1.. (nnd decisions), eq1.. (neq equations).  `periods` is
+a 0-based model period or an inclusive (first, last) pair; None pools every period.  `where=(col, lo, hi)` keeps the
+(agent, period) pairs with lo <= sims[col] <= hi.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+# egdst_moment: 6 ints, then 4 doubles (56 bytes, no padding)
+MOMENT_DTYPE = np.dtype([('kind', '<i4'), ('col', '<i4'), ('col2', '<i4'), ('it_first', '<i4'), ('it_last', '<i4'),
+                         ('cond_col', '<i4'), ('lo', '<f8'), ('hi', '<f8'), ('cond_lo', '<f8'), ('cond_hi', '<f8')])
+
+BASE_COLUMNS = ['M', 'C', 'A', 'V', 'id', 'ist', 'mu', 'sigma', 'shock', 'u', 'df']
+MEAN, CROSS, SHARE = 0, 1, 2
+
+
+def columns(nnst, nnd, neq):
+    """the names of the simulated columns, in order"""
+    return BASE_COLUMNS + ['st%d' % (k + 1) for k in range(nnst)] + ['dc%d' % (k + 1) for k in range(nnd)] + \
+        ['eq%d' % (k + 1) for k in range(neq)]
+
+
+def _layout(layout):
+    """(nnst, nnd, neq) of a library's model info, a Solver / ModelLibrary, a model, or a tuple"""
+    if layout is None:
+        return None
+    for attr in ('lib', 'info'):   # Solver -> ModelLibrary -> EgdstModelInfo
+        if not hasattr(layout, 'nnst') and hasattr(layout, attr):
+            layout = getattr(layout, attr)
+    if hasattr(layout, 'nnst'):   # (a model object counts its equations in _eq)
+        neq = layout.neq if hasattr(layout, 'neq') else len(layout._eq)
+        return int(layout.nnst), int(layout.nnd), int(neq)
+    nnst, nnd, neq = (int(x) for x in layout)
+    return nnst, nnd, neq
+
+
+@dataclass(frozen=True)
+class Moment:
+    kind: int
+    col: object
+    col2: object = None
+    periods: object = None
+    where: object = None
+    lo: float = 0.0
+    hi: float = 0.0
+
+
+def mean(col, periods=None, where=None):
+    """mean of sims[col]"""
+    return Moment(MEAN, col, periods=periods, where=where)
+
+
+def cross(col, col2, periods=None, where=None):
+    """mean of sims[col] * sims[col2] over the pairs where both are present (E[x^2] with col2 = col)"""
+    return Moment(CROSS, col, col2, periods=periods, where=where)
+
+
+def share(col, lo, hi=None, periods=None, where=None):
+    """share of the present values of sims[col] in [lo, hi] (hi = lo when not given): share('id', k) is choice k's share"""
+    return Moment(SHARE, col, periods=periods, where=where, lo=float(lo), hi=float(lo if hi is None else hi))
+
+
+class MomentSpec(list):
+    """A list of Moment records, resolved against a model's column layout (`layout`: the library's model info, a Solver, a
+    ModelLibrary, a model, or (nnst, nnd, neq)).  pack(nt) gives the egdst_moment array; evaluate(sims) the moments of a host panel."""
+
+    def __init__(self, items=(), layout=None):
+        super().__init__(items)
+        self.layout = _layout(layout)
+
+    def names(self, layout=None):
+        lay = _layout(layout) or self.layout
+        if lay is None:
+            raise ValueError('MomentSpec: no column layout (pass layout=(nnst, nnd, neq) or the library)')
+        return columns(*lay)
+
+    @staticmethod
+    def _col(c, names, what):
+        """index of column c; names None: no layout, so only the base tokens resolve and the upper bound is left to the
+        library (or to evaluate, which knows the panel)"""
+        if isinstance(c, str):
+            if c in (names or BASE_COLUMNS):
+                return (names or BASE_COLUMNS).index(c)
+            if names is None and c[:2] in ('st', 'dc', 'eq'):
+                raise ValueError('MomentSpec: column %r of %s needs a layout (layout=(nnst, nnd, neq) or the library)' % (c, what))
+            raise ValueError('MomentSpec: unknown column %r of %s (columns: %s)' % (c, what, ' '.join(names or BASE_COLUMNS)))
+        if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)):
+            raise ValueError('MomentSpec: column %r of %s is neither a name nor an index' % (c, what))
+        if c < 0 or names is not None and c >= len(names):
+            raise ValueError('MomentSpec: column %d of %s is outside [0, %s)' % (c, what, len(names) if names else 'nout'))
+        return int(c)
+
+    def pack(self, nt, layout=None):
+        """[nmom] array of MOMENT_DTYPE; raises ValueError on a bad name, kind, column or period range"""
+        if len(self) == 0:
+            raise ValueError('MomentSpec: no moments')
+        lay = _layout(layout) or self.layout
+        nm = None if lay is None else columns(*lay)
+        out = np.zeros(len(self), dtype=MOMENT_DTYPE)
+        for j, q in enumerate(self):
+            what = 'moment %d' % j
+            if not isinstance(q, Moment) or q.kind not in (MEAN, CROSS, SHARE):
+                raise ValueError('MomentSpec: %s is not a mean, cross or share' % what)
+            col = self._col(q.col, nm, what)
+            col2 = self._col(q.col2, nm, what) if q.kind == CROSS else col
+            if q.periods is None:
+                f, l_ = 0, nt - 1
+            elif isinstance(q.periods, (int, np.integer)) and not isinstance(q.periods, bool):
+                f = l_ = int(q.periods)
+            else:
+                try:
+                    f, l_ = (int(x) for x in q.periods)
+                except (TypeError, ValueError):
+                    raise ValueError('MomentSpec: periods %r of %s is neither a period nor a (first, last) pair'
+                                     % (q.periods, what)) from None
+            if not 0 <= f <= l_ < nt:
+                raise ValueError('MomentSpec: periods (%d, %d) of %s are empty or outside [0, %d)' % (f, l_, what, nt))
+            cc, clo, chi = -1, 0.0, 0.0
+            if q.where is not None:
+                if len(q.where) != 3:
+                    raise ValueError('MomentSpec: where of %s is not (col, lo, hi)' % what)
+                cc = self._col(q.where[0], nm, what)
+                clo, chi = float(q.where[1]), float(q.where[2])
+                if not clo <= chi:
+                    raise ValueError('MomentSpec: where of %s has lo > hi' % what)
+            if q.kind == SHARE and not q.lo <= q.hi:
+                raise ValueError('MomentSpec: share %s has lo > hi' % what)
+            out[j] = (q.kind, col, col2, f, l_, cc, q.lo, q.hi, clo, chi)
+        return out
+
+    def evaluate(self, sims, block=256, layout=None):
+        """(means [nmom], counts [nmom]) of a host panel sims [nsim, nt, nout] (NaN = missing) with the definitions and the
+        summation order of the device (include/egdst.h): per partial t < block the agents i = t (mod block) in ascending i,
+        periods ascending within an agent, then the fixed tree over the partials.  block=256 is the GPU's."""
+        sims = np.asarray(sims, dtype=np.float64)
+        if sims.ndim != 3:
+            raise ValueError('MomentSpec.evaluate: sims must be [nsim, nt, nout]')
+        if block < 1 or block & (block - 1):
+            raise ValueError('MomentSpec.evaluate: block must be a power of two')
+        nsim, nt, nout = sims.shape
+        lay = _layout(layout) or self.layout
+        if lay is not None and 11 + sum(lay) != nout:
+            raise ValueError('MomentSpec.evaluate: the panel has %d columns, the layout %d' % (nout, 11 + sum(lay)))
+        rec = self.pack(nt, layout)
+        if (rec['col'].max(initial=0) >= nout or rec['col2'].max(initial=0) >= nout or rec['cond_col'].max(initial=-1) >= nout):
+            raise ValueError('MomentSpec.evaluate: a column is outside the panel\'s %d columns' % nout)
+        nb = -(-nsim // block)
+        means = np.empty(len(rec))
+        counts = np.empty(len(rec), dtype=np.int64)
+        for j, q in enumerate(rec):
+            f, l_ = int(q['it_first']), int(q['it_last']) + 1
+            v = sims[:, f:l_, q['col']]
+            ok = ~np.isnan(v)
+            if q['cond_col'] >= 0:
+                c = sims[:, f:l_, q['cond_col']]
+                ok &= (c >= q['cond_lo']) & (c <= q['cond_hi'])
+            if q['kind'] == CROSS:
+                w = sims[:, f:l_, q['col2']]
+                ok &= ~np.isnan(w)
+                x = v * w
+            elif q['kind'] == SHARE:
+                x = ((v >= q['lo']) & (v <= q['hi'])).astype(np.float64)
+            else:
+                x = v
+            x = np.where(ok, x, 0.0)   # (adding +0.0 leaves a partial unchanged: it starts at +0.0 and never becomes -0.0)
+            # partial t adds agents t, t+block, ... in order, each agent's periods in order: [block, nb * periods] rows
+            xp = np.zeros((nb * block, l_ - f))
+            xp[:nsim] = x
+            rows = xp.reshape(nb, block, l_ - f).transpose(1, 0, 2).reshape(block, -1)
+            p = np.cumsum(rows, axis=1)[:, -1].copy() if rows.shape[1] else np.zeros(block)
+            n = ok.sum()
+            o = block // 2
+            while o > 0:
+                p[:o] += p[o:2 * o]
+                o //= 2
+            counts[j] = n
+            means[j] = p[0] / n if n else np.nan
+        return means, counts
+
+
+def objective(means, counts, target, W):
+    """e' W e in the device's order (k_moment_objective_w): e = means - target, r_j = sum over k ascending of the non-zero
+    W_jk * e_k, obj = sum over j ascending of e_j * r_j over the rows with a non-zero entry; NaN if a moment W touches is
+    empty.  means/counts [nmom] or [ndraw, nmom]; W [nmom, nmom] or a vector (its diagonal)."""
+    means, counts = np.asarray(means, dtype=np.float64), np.asarray(counts)
+    if means.ndim == 2:
+        return np.array([objective(m, c, target, W) for m, c in zip(means, counts)])
+    n = len(means)
+    W = weight_matrix(W, n)
+    e = means - np.asarray(target, dtype=np.float64).reshape(-1)
+    nz = W != 0
+    if np.any((counts == 0) & (nz.any(axis=0) | nz.any(axis=1))):
+        return np.nan
+    acc = 0.0
+    for j in range(n):
+        k = np.nonzero(nz[j])[0]
+        if len(k):
+            r = float(np.cumsum(W[j, k] * e[k])[-1])
+            acc += float(e[j]) * r
+    return acc
+
+
+def weight_matrix(W, nmom):
+    """W as a C-ordered [nmom, nmom] float64 matrix (a vector is its diagonal)"""
+    W = np.asarray(W, dtype=np.float64)
+    if W.ndim == 1:
+        W = np.diag(W)
+    if W.shape != (nmom, nmom):
+        raise ValueError('W must be [%d, %d] or a vector of %d' % (nmom, nmom, nmom))
+    return np.ascontiguousarray(W)

@@ -34,7 +34,8 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_create_compact', 'egdst_geometry', 'egdst_set_groups', 'egdst_set_adaptive', 'egdst_get_schedule', 'egdst_get_work', 'egdst_get_regenerations', 'egdst_call', 'egdst_simulate_moments',
                'egdst_get_checksums', 'egdst_math_eval', 'egdst_get_evals_credited', 'egdst_simulate_batch_moments',
                'egdst_uniform', 'egdst_set_dbgout', 'egdst_get_dbgout', 'egdst_get_walk_stats',
-               'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_group_profile']
+               'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_group_profile',
+               'egdst_simulate_batch_spec']
 
 
 class EgdstRuntimeError(RuntimeError):
@@ -85,6 +86,9 @@ class ModelLibrary:
         L.egdst_get_evals_credited.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
         L.egdst_simulate_batch_moments.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_longlong, C.c_ulonglong,
                                                    C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.egdst_simulate_batch_spec.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_longlong, C.c_ulonglong,
+                                                C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
         L.egdst_uniform.restype = C.c_double
         L.egdst_uniform.argtypes = [C.c_ulonglong, C.c_ulonglong]
         L.egdst_set_dbgout.argtypes = [C.c_void_p, C.c_int]
@@ -513,6 +517,50 @@ class Solver:
             C.c_void_p(counts_dev) if counts_dev else None, C.c_void_p(obj_dev) if obj_dev else None))
         if own:
             return tm.cpu().numpy(), tc.cpu().numpy(), to.cpu().numpy()
+        return None
+
+    def simulate_batch_spec(self, init, spec, seed=0, rndtype=0, target=None, W=None, randstream_dev=None, nrand=0,
+                            means_dev=None, counts_dev=None, obj_dev=None):
+        """egdst_simulate_batch_spec: the estimation step of simulate_batch_moments with user-defined moments -- spec is a
+        moments.MomentSpec (names resolved with this library's columns) or an array of moments.MOMENT_DTYPE -- and a full
+        weighting matrix W ([nmom, nmom], or a vector: its diagonal).  The objective is computed when target and W are given.
+        The *_dev arguments are device pointers (ints); with none given, returns (means [ndraw, nmom], counts [ndraw, nmom],
+        objective [ndraw] or None) through torch tensors allocated here."""
+        from . import moments
+        init = np.asfortranarray(np.atleast_2d(np.asarray(init, dtype=np.float64)))
+        if isinstance(spec, moments.MomentSpec):
+            rec = spec.pack(self.nt, layout=self.lib.info)
+        else:
+            rec = np.ascontiguousarray(spec, dtype=moments.MOMENT_DTYPE).reshape(-1)
+        nmom = len(rec)
+        if (target is None) != (W is None):
+            raise EgdstRuntimeError(1, 'simulate_batch_spec: the objective needs both target and W')
+        t = w = None
+        if W is not None:
+            t = np.ascontiguousarray(target, dtype=np.float64).reshape(-1)
+            if t.size != nmom:
+                raise EgdstRuntimeError(1, 'simulate_batch_spec: target has %d entries for %d moments' % (t.size, nmom))
+            try:
+                w = moments.weight_matrix(W, nmom)
+            except ValueError as e:
+                raise EgdstRuntimeError(1, 'simulate_batch_spec: %s' % e) from None
+        own = means_dev is None and counts_dev is None and obj_dev is None
+        if own:
+            import torch
+            tm = torch.zeros(self.ndraw, nmom, dtype=torch.float64, device='cuda')
+            tc = torch.zeros(self.ndraw, nmom, dtype=torch.int32, device='cuda')
+            to = torch.zeros(self.ndraw, dtype=torch.float64, device='cuda') if w is not None else None
+            # torch fills them on ITS stream, the library writes them on the handle's (as in simulate_batch_moments)
+            torch.cuda.current_stream().synchronize()
+            means_dev, counts_dev = tm.data_ptr(), tc.data_ptr()
+            obj_dev = to.data_ptr() if to is not None else None
+        self.lib.check(self.lib.lib.egdst_simulate_batch_spec(
+            self.h, _dp(init), init.shape[0], C.c_void_p(randstream_dev) if randstream_dev else None, int(nrand), int(seed),
+            int(rndtype), rec.ctypes.data_as(C.c_void_p), nmom, _dp(t) if t is not None else None,
+            _dp(w) if w is not None else None, C.c_void_p(means_dev) if means_dev else None,
+            C.c_void_p(counts_dev) if counts_dev else None, C.c_void_p(obj_dev) if obj_dev else None))
+        if own:
+            return tm.cpu().numpy(), tc.cpu().numpy(), to.cpu().numpy() if to is not None else None
         return None
 
     def call(self, sw, args, draw=0):

@@ -185,6 +185,38 @@ int egdst_simulate_moments(egdst_handle *h, int draw, const double *init, int ns
 int egdst_simulate_batch_moments(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
                                  long long nrand, unsigned long long seed, int rndtype, const double *target,
                                  const double *weight, double *means_dev, int *counts_dev, double *obj_dev);
+/* One simulated moment of the estimation step.  Over the (agent, period) pairs with it_first <= it <= it_last whose
+ * value is present (not NaN) and, if cond_col >= 0, with cond_lo <= sims[cond_col] <= cond_hi (NaN never qualifies):
+ *   kind 0  mean of sims[col]
+ *   kind 1  mean of sims[col] * sims[col2]                      (both present)
+ *   kind 2  share with lo <= sims[col] <= hi among those pairs  (a choice share: col = 4, lo = hi = k)
+ * Columns are 0-based as in egdst_simulate (nout = 11+nnst+nnd+neq); periods are 0-based model periods. */
+typedef struct {
+    int kind, col, col2, it_first, it_last, cond_col;
+    double lo, hi, cond_lo, cond_hi;
+} egdst_moment;   /* 56 bytes */
+
+/* The estimation step with user-defined moments and a full weighting matrix (new surface).  Simulation,
+ * uniforms, rndtype, common random numbers, slicing and failed draws exactly as egdst_simulate_batch_moments; per draw:
+ *   means_dev [ndraw][nmom], counts_dev [ndraw][nmom]   moment j of spec[j]; NaN mean / 0 count where no pair qualifies
+ *   obj_dev   [ndraw]   e' W e, e_j = mean_j - target_j (target: host [nmom], W: host [nmom x nmom] row-major); NaN if a
+ *                       moment with a non-zero entry in its row or column of W has count 0
+ * All three are DEVICE buffers and may be NULL, but one of them must be given; obj_dev needs target and W.
+ * Summation order (part of the contract; B = 256, the moment kernel's block size):
+ *   partial t (0 <= t < B) starts at 0.0 and adds the qualifying values of the agents i = t (mod B) in ascending i, within
+ *   an agent in ascending period (kind 2 adds 1.0 or 0.0); then for o = B/2 .. 1: p[t] += p[t+o] (t < o); mean = p[0] / count.
+ *   A kind-0 moment over one period without condition is exactly the egdst_simulate_batch_moments cell.
+ *   r_j = sum over k ascending of W_jk * e_k, skipping W_jk == 0; obj = sum over j ascending of e_j * r_j, skipping the j
+ *   whose row of W is all zero (a diagonal W gives the bits of egdst_simulate_batch_moments' objective).
+ * EGDST_E_ARG before anything is launched if a kind is not 0..2, a column is outside [0, nout) (cond_col -1: no
+ * condition), a period range is empty or outside [0, nt), nmom <= 0, nsim times the periods of a moment exceeds INT_MAX,
+ * obj_dev is given without target and W, or no output is given. */
+int egdst_simulate_batch_spec(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
+                              long long nrand, unsigned long long seed, int rndtype,
+                              const egdst_moment *spec, int nmom,
+                              const double *target /* [nmom] */, const double *W /* [nmom x nmom] row-major */,
+                              double *means_dev /* [ndraw][nmom] */, int *counts_dev /* [ndraw][nmom] */,
+                              double *obj_dev /* [ndraw] */);
 /* Uniform number k of stream `seed` (host replay of the device generator): with z = seed + (k+1)*0x9E3779B97F4A7C15,
  * z = (z ^ z>>30)*0xBF58476D1CE4E5B9, z = (z ^ z>>27)*0x94D049BB133111EB, z ^= z>>31 (splitmix64): (z >> 11) * 2^-53. */
 double egdst_uniform(unsigned long long seed, unsigned long long k);
