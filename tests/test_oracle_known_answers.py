@@ -1,8 +1,8 @@
 """Pin the CPU oracle to the reference outputs recorded in SURVEY.md §8(c).
 
-The reference ships no tests or golden vectors and cannot be built in this image
-without stand-ins for MATLAB's mex.h and MATLAB-generated modelspec.c, so these recorded values of
-the five shipped example models are the known answers the oracle is held to.
+The reference ships no tests or golden vectors.  These values of the five shipped example models were
+written down by the survey; they stay as known answers.  The oracle is held to a live build of the reference's own C,
+in full and bit for bit, by tests/test_reference_parity.py (oracle/build_ref.py builds it on a small MEX host).
 """
 import json
 import os
