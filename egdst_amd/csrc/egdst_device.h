@@ -19,6 +19,7 @@
 #define EG_ZEROC MS_ZEROCONSUMPTION
 #define EG_DPD MS_DOUBLEPOINT_DELTA
 #define EG_A0T 0.0  // egdst_solver.c:49
+#define EG_NOUT (11 + MS_NNST + MS_NND + MS_NEQ)  // columns of a simulated path (egdst_simulate: nsimout)
 
 // ---- problem geometry shared by all kernels -------------------------------------------------
 struct Geom {

@@ -65,11 +65,11 @@ struct egdst_handle {
     Batch *b_dev;      // device copies of `b` the kernels read (constant address space): one per draw group with its draw0,
     Batch *b_host;     // and entry EGDST_MAX_GROUPS for the launches outside a solve; pinned staging of the same
     // simulator buffers, grown on demand and kept (egdst_simulate*, egdst_simulate_batch_moments, egdst_simulate_batch_spec)
-    double *sim_init, *sim_rs, *sim_sims, *sim_means, *sim_tw;
+    double *sim_init, *sim_rs, *sim_sims, *sim_means;
     int *sim_err, *sim_counts;
-    size_t sim_init_bytes, sim_rs_bytes, sim_sims_bytes, sim_means_bytes, sim_tw_bytes, sim_err_bytes, sim_counts_bytes;
-    egdst_moment *sim_spec;     // egdst_simulate_batch_spec: the moment records, target and weighting matrix
-    double *sim_tgt, *sim_W;
+    size_t sim_init_bytes, sim_rs_bytes, sim_sims_bytes, sim_means_bytes, sim_err_bytes, sim_counts_bytes;
+    egdst_moment *sim_spec;     // estimation_step: the moment records (egdst_simulate_batch_spec), the target and the weighting
+    double *sim_tgt, *sim_W;    // matrix, or its diagonal (egdst_simulate_batch_moments)
     size_t sim_spec_bytes, sim_tgt_bytes, sim_W_bytes;
     size_t klog_bytes;  // kink log (egdst_set_dbgout), allocated apart from the pool
     void **emu_items;  // sanitizer harness only: one heap block per array instead of the pool
@@ -681,7 +681,7 @@ extern "C" int egdst_destroy(egdst_handle *h)
     if (h->b.klog) (void)hipFree(h->b.klog);
     if (h->b.kcnt) (void)hipFree(h->b.kcnt);
     {
-        void *simbufs[] = {h->sim_init, h->sim_rs, h->sim_sims, h->sim_means, h->sim_tw, h->sim_err, h->sim_counts,
+        void *simbufs[] = {h->sim_init, h->sim_rs, h->sim_sims, h->sim_means, h->sim_err, h->sim_counts,
                            h->sim_spec, h->sim_tgt, h->sim_W};
         for (void *p : simbufs)
             if (p) (void)hipFree(p);
@@ -1338,8 +1338,7 @@ static int run_simulation(egdst_handle *h, int draw0, int nd, int batch, const d
     rc = sim_check(h, init, nsim, nrand, rndtype, randstream != nullptr || rs_dev != nullptr);
     if (rc) return rc;
     const Geom &g = h->b.g;
-    const int nout = 11 + MS_NNST + MS_NND + MS_NEQ;
-    const size_t per_draw = (size_t)nout * g.nt * nsim, nsims = per_draw * nd;
+    const size_t per_draw = (size_t)EG_NOUT * g.nt * nsim, nsims = per_draw * nd;
     const long long nuse = (rndtype == 1) ? 4LL * g.nt : 4LL * nsim * g.nt;
     rc = sim_reserve((void **)&h->sim_init, &h->sim_init_bytes, sizeof(double) * 2 * nsim);
     if (!rc && randstream) rc = sim_reserve((void **)&h->sim_rs, &h->sim_rs_bytes, sizeof(double) * nuse);
@@ -1359,7 +1358,7 @@ static int run_simulation(egdst_handle *h, int draw0, int nd, int batch, const d
     a.draw = draw0;
     a.nsim = nsim;
     a.rndtype = rndtype;
-    a.nout = nout;
+    a.nout = EG_NOUT;
     a.batch = batch;
     a.init = h->sim_init;
     a.randstream = randstream ? h->sim_rs : rs_dev;
@@ -1380,7 +1379,7 @@ extern "C" int egdst_simulate(egdst_handle *h, int draw, const double *init, int
     if (!sims || !randstream) return set_err(EGDST_E_ARG, "egdst_simulate: bad arguments");
     int rc = run_simulation(h, draw, 1, 0, init, nsim, randstream, nullptr, nrand, 0ull, rndtype);
     if (rc) return rc;
-    const size_t nsims = (size_t)(11 + MS_NNST + MS_NND + MS_NEQ) * h->b.g.nt * nsim;
+    const size_t nsims = (size_t)EG_NOUT * h->b.g.nt * nsim;
     HIPCHK(hipMemcpy(sims, h->sim_sims, sizeof(double) * nsims, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1394,12 +1393,12 @@ extern "C" int egdst_simulate_moments(egdst_handle *h, int draw, const double *i
     if (!means || !counts || !randstream) return set_err(EGDST_E_ARG, "egdst_simulate_moments: bad arguments");
     int rc = run_simulation(h, draw, 1, 0, init, nsim, randstream, nullptr, nrand, 0ull, rndtype);
     if (rc) return rc;
-    const int nout = 11 + MS_NNST + MS_NND + MS_NEQ, ncell = nout * h->b.g.nt;
+    const int nt = h->b.g.nt, ncell = EG_NOUT * nt;
     rc = sim_reserve((void **)&h->sim_means, &h->sim_means_bytes, sizeof(double) * ncell);
     if (!rc) rc = sim_reserve((void **)&h->sim_counts, &h->sim_counts_bytes, sizeof(int) * ncell);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_moments, dim3(ncell), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_sims, nsim, ncell, h->sim_means,
-                       h->sim_counts);
+    hipLaunchKernelGGL(k_moments, dim3(ncell), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_sims, nsim, nt,
+                       (const egdst_moment *)nullptr, ncell, h->sim_means, h->sim_counts);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(means, h->sim_means, sizeof(double) * ncell, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(counts, h->sim_counts, sizeof(int) * ncell, hipMemcpyDeviceToHost, h->stream));
@@ -1412,68 +1411,69 @@ extern "C" double egdst_uniform(unsigned long long seed, unsigned long long k) {
 #ifndef EG_SIM_SLICE_BYTES
 #define EG_SIM_SLICE_BYTES (2ull << 30)
 #endif
-// The slice loop of the estimation step: draws [d0, d0+nd) are simulated together as long as their paths fit
-// EG_SIM_SLICE_BYTES, and reduce(d0, nd) enqueues the slice's reduction on the handle's stream before the next slice
-// overwrites the paths (run_simulation waits for its kernel, so the reduction of a slice precedes the next fill).
-template <class Reduce>
-static int simulate_slices(egdst_handle *h, const double *init, int nsim, const double *randstream_dev, long long nrand,
-                           unsigned long long seed, int rndtype, Reduce reduce)
+// The estimation step on the device, behind egdst_simulate_batch_moments and egdst_simulate_batch_spec (which check their
+// arguments): every draw of the handle is simulated with the same agents and the same uniforms (common random numbers),
+// k_moments reduces the paths to nmom moments per draw and k_moment_objective forms the draw's distance to the target.
+// spec == nullptr: the moments are the nmom = EG_NOUT * nt per-period cells and W [nmom] is the diagonal of the weighting;
+// otherwise spec [nmom] (host) and W [nmom x nmom].  Draws [d0, d0+nd) are simulated together as long as their paths fit
+// EG_SIM_SLICE_BYTES, and a slice is reduced on the handle's stream before the next one overwrites the paths
+// (run_simulation waits for its kernel).  Nothing but the objective and, if asked for, the moments is written for the caller.
+static int estimation_step(egdst_handle *h, const double *init, int nsim, const double *randstream_dev, long long nrand,
+                           unsigned long long seed, int rndtype, const egdst_moment *spec, int nmom, const double *target,
+                           const double *W, double *means_dev, int *counts_dev, double *obj_dev)
 {
     const Geom &g = h->b.g;
-    const size_t per_draw = sizeof(double) * (size_t)(11 + MS_NNST + MS_NND + MS_NEQ) * g.nt * nsim;
+    const size_t nW = spec ? (size_t)nmom * nmom : (size_t)nmom;
+    int rc = sim_reserve((void **)&h->sim_means, &h->sim_means_bytes, sizeof(double) * (size_t)nmom * g.ndraw);
+    if (!rc) rc = sim_reserve((void **)&h->sim_counts, &h->sim_counts_bytes, sizeof(int) * (size_t)nmom * g.ndraw);
+    if (!rc && spec) rc = sim_reserve((void **)&h->sim_spec, &h->sim_spec_bytes, sizeof(egdst_moment) * (size_t)nmom);
+    if (!rc && obj_dev) rc = sim_reserve((void **)&h->sim_tgt, &h->sim_tgt_bytes, sizeof(double) * (size_t)nmom);
+    if (!rc && obj_dev) rc = sim_reserve((void **)&h->sim_W, &h->sim_W_bytes, sizeof(double) * nW);
+    if (rc) return rc;
+    if (spec) HIPCHK(hipMemcpyAsync(h->sim_spec, spec, sizeof(egdst_moment) * (size_t)nmom, hipMemcpyHostToDevice, h->stream));
+    if (obj_dev) {
+        HIPCHK(hipMemcpyAsync(h->sim_tgt, target, sizeof(double) * (size_t)nmom, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->sim_W, W, sizeof(double) * nW, hipMemcpyHostToDevice, h->stream));
+    }
+    const size_t per_draw = sizeof(double) * (size_t)EG_NOUT * g.nt * nsim;
     int slice = (int)(EG_SIM_SLICE_BYTES / (per_draw ? per_draw : 1));
     if (slice < 1) slice = 1;
     if (slice > g.ndraw) slice = g.ndraw;
     for (int d0 = 0; d0 < g.ndraw; d0 += slice) {
         const int nd = (g.ndraw - d0 < slice) ? g.ndraw - d0 : slice;
-        int rc = run_simulation(h, d0, nd, 1, init, nsim, nullptr, randstream_dev, nrand, seed, rndtype);
+        rc = run_simulation(h, d0, nd, 1, init, nsim, nullptr, randstream_dev, nrand, seed, rndtype);
         if (rc) return rc;
-        reduce(d0, nd);
+        hipLaunchKernelGGL(k_moments, dim3(nmom, nd), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_sims, nsim, g.nt,
+                           spec ? (const egdst_moment *)h->sim_spec : nullptr, nmom, h->sim_means + (size_t)d0 * nmom,
+                           h->sim_counts + (size_t)d0 * nmom);
     }
+    if (obj_dev)
+        hipLaunchKernelGGL(k_moment_objective, dim3(g.ndraw), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_means,
+                           (const int *)h->sim_counts, nmom, (const double *)h->sim_tgt, (const double *)h->sim_W, spec ? 0 : 1,
+                           obj_dev);
+    HIPCHK(hipGetLastError());
+    if (means_dev)
+        HIPCHK(hipMemcpyAsync(means_dev, h->sim_means, sizeof(double) * (size_t)nmom * g.ndraw, hipMemcpyDeviceToDevice, h->stream));
+    if (counts_dev)
+        HIPCHK(hipMemcpyAsync(counts_dev, h->sim_counts, sizeof(int) * (size_t)nmom * g.ndraw, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
 }
 
-// The estimation step on the device: every draw of the handle is simulated with the same agents and the same uniforms
-// (common random numbers), per-period means of every simulated column are reduced per draw, and the objective of a
-// draw is its weighted squared distance to the target moments.  Draws are processed in slices whose paths fit
-// EG_SIM_SLICE_BYTES; nothing but the objective (and, if asked for, the moments) is written for the caller.
+// The step with the fixed moments: per-period means of every simulated column, and the weighted squared distance to the
+// target moments as the objective of a draw.
 extern "C" int egdst_simulate_batch_moments(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
                                             long long nrand, unsigned long long seed, int rndtype, const double *target,
                                             const double *weight, double *means_dev, int *counts_dev, double *obj_dev)
 {
     if (!h || (obj_dev && (!target || !weight)) || (!obj_dev && !means_dev))
         return set_err(EGDST_E_ARG, "egdst_simulate_batch_moments: bad arguments");
-    const Geom &g = h->b.g;
-    const int nout = 11 + MS_NNST + MS_NND + MS_NEQ, ncell = nout * g.nt;
-    int rc = sim_reserve((void **)&h->sim_means, &h->sim_means_bytes, sizeof(double) * (size_t)ncell * g.ndraw);
-    if (!rc) rc = sim_reserve((void **)&h->sim_counts, &h->sim_counts_bytes, sizeof(int) * (size_t)ncell * g.ndraw);
-    if (!rc && obj_dev) rc = sim_reserve((void **)&h->sim_tw, &h->sim_tw_bytes, sizeof(double) * 2 * ncell);
-    if (rc) return rc;
-    if (obj_dev) {
-        HIPCHK(hipMemcpyAsync(h->sim_tw, target, sizeof(double) * ncell, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->sim_tw + ncell, weight, sizeof(double) * ncell, hipMemcpyHostToDevice, h->stream));
-    }
-    rc = simulate_slices(h, init, nsim, randstream_dev, nrand, seed, rndtype, [&](int d0, int nd) {
-        hipLaunchKernelGGL(k_moments, dim3(ncell, nd), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_sims, nsim, ncell,
-                           h->sim_means + (size_t)d0 * ncell, h->sim_counts + (size_t)d0 * ncell);
-    });
-    if (rc) return rc;
-    if (obj_dev)
-        hipLaunchKernelGGL(k_moment_objective, dim3((g.ndraw + 63) / 64), dim3(64), 0, h->stream, (const double *)h->sim_means,
-                           (const int *)h->sim_counts, ncell, (const double *)h->sim_tw, (const double *)(h->sim_tw + ncell), g.ndraw,
-                           obj_dev);
-    HIPCHK(hipGetLastError());
-    if (means_dev)
-        HIPCHK(hipMemcpyAsync(means_dev, h->sim_means, sizeof(double) * (size_t)ncell * g.ndraw, hipMemcpyDeviceToDevice, h->stream));
-    if (counts_dev)
-        HIPCHK(hipMemcpyAsync(counts_dev, h->sim_counts, sizeof(int) * (size_t)ncell * g.ndraw, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return estimation_step(h, init, nsim, randstream_dev, nrand, seed, rndtype, nullptr, EG_NOUT * h->b.g.nt, target, weight,
+                           means_dev, counts_dev, obj_dev);
 }
 
-// The estimation step with user-defined moments (egdst_moment) and a full weighting matrix: the simulation and its slices
-// are those of egdst_simulate_batch_moments, k_moments_spec reduces each slice's paths to the spec's moments and
-// k_moment_objective_w forms e' W e per draw.  Every argument is checked before anything is enqueued.
+// The step with user-defined moments (egdst_moment) and a full weighting matrix: the objective is e' W e.  Every argument
+// is checked before anything is enqueued.
 static_assert(sizeof(egdst_moment) == 56, "egdst_moment is 6 ints and 4 doubles (the Python dtype mirrors it)");
 extern "C" int egdst_simulate_batch_spec(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
                                          long long nrand, unsigned long long seed, int rndtype, const egdst_moment *spec,
@@ -1482,8 +1482,7 @@ extern "C" int egdst_simulate_batch_spec(egdst_handle *h, const double *init, in
 {
     if (!h || !spec || nmom <= 0 || (obj_dev && (!target || !W)) || (!obj_dev && !means_dev && !counts_dev))
         return set_err(EGDST_E_ARG, "egdst_simulate_batch_spec: bad arguments");
-    const Geom &g = h->b.g;
-    const int nout = 11 + MS_NNST + MS_NND + MS_NEQ;
+    const int nout = EG_NOUT, nt = h->b.g.nt;
     for (int j = 0; j < nmom; j++) {
         const egdst_moment &q = spec[j];
         const char *bad = nullptr;
@@ -1491,37 +1490,12 @@ extern "C" int egdst_simulate_batch_spec(egdst_handle *h, const double *init, in
         else if (q.col < 0 || q.col >= nout) bad = "col is outside the simulated columns";
         else if (q.col2 < 0 || q.col2 >= nout) bad = "col2 is outside the simulated columns";
         else if (q.cond_col < -1 || q.cond_col >= nout) bad = "cond_col is outside the simulated columns";
-        else if (q.it_first < 0 || q.it_last < q.it_first || q.it_last >= g.nt) bad = "the period range is empty or outside the model's";
+        else if (q.it_first < 0 || q.it_last < q.it_first || q.it_last >= nt) bad = "the period range is empty or outside the model's";
         else if (nsim > 0 && (long long)nsim * (q.it_last - q.it_first + 1) > 2147483647LL) bad = "nsim times its periods overflows a count";
         if (bad) return set_err(EGDST_E_ARG, "egdst_simulate_batch_spec: moment %d: %s", j, bad);
     }
-    int rc = sim_reserve((void **)&h->sim_means, &h->sim_means_bytes, sizeof(double) * (size_t)nmom * g.ndraw);
-    if (!rc) rc = sim_reserve((void **)&h->sim_counts, &h->sim_counts_bytes, sizeof(int) * (size_t)nmom * g.ndraw);
-    if (!rc) rc = sim_reserve((void **)&h->sim_spec, &h->sim_spec_bytes, sizeof(egdst_moment) * (size_t)nmom);
-    if (!rc && obj_dev) rc = sim_reserve((void **)&h->sim_tgt, &h->sim_tgt_bytes, sizeof(double) * (size_t)nmom);
-    if (!rc && obj_dev) rc = sim_reserve((void **)&h->sim_W, &h->sim_W_bytes, sizeof(double) * (size_t)nmom * nmom);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h->sim_spec, spec, sizeof(egdst_moment) * (size_t)nmom, hipMemcpyHostToDevice, h->stream));
-    if (obj_dev) {
-        HIPCHK(hipMemcpyAsync(h->sim_tgt, target, sizeof(double) * (size_t)nmom, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->sim_W, W, sizeof(double) * (size_t)nmom * nmom, hipMemcpyHostToDevice, h->stream));
-    }
-    rc = simulate_slices(h, init, nsim, randstream_dev, nrand, seed, rndtype, [&](int d0, int nd) {
-        hipLaunchKernelGGL(k_moments_spec, dim3(nmom, nd), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_sims, nsim, g.nt,
-                           nout, (const egdst_moment *)h->sim_spec, nmom, h->sim_means + (size_t)d0 * nmom,
-                           h->sim_counts + (size_t)d0 * nmom);
-    });
-    if (rc) return rc;
-    if (obj_dev)
-        hipLaunchKernelGGL(k_moment_objective_w, dim3(g.ndraw), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_means,
-                           (const int *)h->sim_counts, nmom, (const double *)h->sim_tgt, (const double *)h->sim_W, obj_dev);
-    HIPCHK(hipGetLastError());
-    if (means_dev)
-        HIPCHK(hipMemcpyAsync(means_dev, h->sim_means, sizeof(double) * (size_t)nmom * g.ndraw, hipMemcpyDeviceToDevice, h->stream));
-    if (counts_dev)
-        HIPCHK(hipMemcpyAsync(counts_dev, h->sim_counts, sizeof(int) * (size_t)nmom * g.ndraw, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return estimation_step(h, init, nsim, randstream_dev, nrand, seed, rndtype, spec, nmom, target, W, means_dev, counts_dev,
+                           obj_dev);
 }
 
 // egdst_call.c:17-164.  The index checks of the gateway are done here, in row order, because an out-of-range index

@@ -4796,75 +4796,34 @@ __global__ void __launch_bounds__(GRID_BS) k_call(const Batch *bp_, CallArgs a)
     a.res[i] = r;
 }
 
-// Mean of one (column, period) cell of the simulated paths over the agents that have a value there (the others are NaN:
-// died, or started outside the admissible range).  One workgroup per cell; each thread adds its agents in index order,
-// then a fixed tree over the threads: the result does not depend on scheduling.
 #ifdef EGDST_EMU
 #define MOM_BS 1
 #else
 #define MOM_BS 256
 #endif
-__global__ void __launch_bounds__(MOM_BS) k_moments(const double *sims, int nsim, int ncell, double *means, int *counts)
+// Moment j of the fixed set, the mean of one (column, period) cell of the paths: j = col + nout * it.
+static __device__ __forceinline__ egdst_moment eg_cell_moment(int j)
 {
-    __shared__ double ssum[MOM_BS];
-    __shared__ int scnt[MOM_BS];
-    const int cell = blockIdx.x, tid = threadIdx.x;
-    sims += (size_t)blockIdx.y * ncell * nsim;   // (one set of paths, means and counts per draw of the launch)
-    means += (size_t)blockIdx.y * ncell;
-    counts += (size_t)blockIdx.y * ncell;
-    double acc = 0;
-    int cnt = 0;
-    for (int i = tid; i < nsim; i += MOM_BS) {
-        const double v = sims[(size_t)cell + (size_t)ncell * i];
-        if (v == v) acc += v, cnt++;
-    }
-    ssum[tid] = acc;
-    scnt[tid] = cnt;
-    __syncthreads();
-    for (int o = MOM_BS / 2; o > 0; o >>= 1) {
-        if (tid < o) ssum[tid] += ssum[tid + o], scnt[tid] += scnt[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        counts[cell] = scnt[0];
-        means[cell] = scnt[0] ? ssum[0] / scnt[0] : NAN;
-    }
+    egdst_moment q = {};
+    q.col = j % EG_NOUT;
+    q.it_first = q.it_last = j / EG_NOUT;
+    q.cond_col = -1;
+    return q;
 }
 
-// Distance of one draw's simulated moments to the targets: sum over the cells with a non-zero weight of
-// weight * (mean - target)^2, added in cell order by one thread per draw (deterministic); NaN if a weighted cell is empty.
-__global__ void k_moment_objective(const double *means, const int *counts, int ncell, const double *target, const double *weight,
-                                   int ndraw, double *obj)
-{
-    const int d = blockIdx.x * blockDim.x + threadIdx.x;
-    if (d >= ndraw) return;
-    const double *m = means + (size_t)d * ncell;
-    const int *c = counts + (size_t)d * ncell;
-    double acc = 0;
-    for (int k = 0; k < ncell; k++) {
-        if (weight[k] == 0.0) continue;
-        if (c[k] == 0) {
-            acc = NAN;
-            break;
-        }
-        const double e = m[k] - target[k];
-        acc += weight[k] * e * e;
-    }
-    obj[d] = acc;
-}
-
-// One user-defined moment (egdst_moment, include/egdst.h) of one draw's simulated paths.  One workgroup per (moment, draw
-// of the slice); each thread adds the qualifying values of its agents in index order, within an agent in period order,
-// then the same fixed tree as k_moments: a kind-0 moment of one period without condition is exactly k_moments' cell.
-__global__ void __launch_bounds__(MOM_BS) k_moments_spec(const double *sims, int nsim, int nt, int nout, const egdst_moment *spec,
-                                                         int nmom, double *means, int *counts)
+// One moment (egdst_moment, include/egdst.h) of one draw's simulated paths: spec[j], or with spec == nullptr cell j of the
+// fixed set.  The agents without a value (NaN: died, or started outside the admissible range) do not count.  One workgroup
+// per (moment, draw of the launch); each thread adds the qualifying values of its agents in index order, within an agent in
+// period order, then a fixed tree over the threads: the result does not depend on scheduling.
+__global__ void __launch_bounds__(MOM_BS) k_moments(const double *sims, int nsim, int nt, const egdst_moment *spec, int nmom,
+                                                    double *means, int *counts)
 {
     __shared__ double ssum[MOM_BS];
     __shared__ int scnt[MOM_BS];
     const int j = blockIdx.x, tid = threadIdx.x;
-    const egdst_moment q = spec[j];
-    const size_t per_agent = (size_t)nout * nt;
-    sims += (size_t)blockIdx.y * per_agent * nsim;
+    const egdst_moment q = spec ? spec[j] : eg_cell_moment(j);
+    const size_t per_agent = (size_t)EG_NOUT * nt;
+    sims += (size_t)blockIdx.y * per_agent * nsim;   // (one set of paths, means and counts per draw of the launch)
     means += (size_t)blockIdx.y * nmom;
     counts += (size_t)blockIdx.y * nmom;
     double acc = 0;
@@ -4872,7 +4831,7 @@ __global__ void __launch_bounds__(MOM_BS) k_moments_spec(const double *sims, int
     for (int i = tid; i < nsim; i += MOM_BS) {
         const double *p = sims + (size_t)i * per_agent;
         for (int it = q.it_first; it <= q.it_last; it++) {
-            const double *o = p + (size_t)it * nout;
+            const double *o = p + (size_t)it * EG_NOUT;
             const double v = o[q.col];
             if (!(v == v)) continue;
             if (q.cond_col >= 0) {
@@ -4903,13 +4862,14 @@ __global__ void __launch_bounds__(MOM_BS) k_moments_spec(const double *sims, int
     }
 }
 
-// Quadratic form e' W e of one draw's moments, e = means - target, W [nmom x nmom] row-major: r_j = sum over the non-zero
-// W_jk in k order of W_jk * e_k, obj = sum over the rows with a non-zero entry in j order of e_j * r_j; NaN if a moment that
-// W touches (row or column) is empty.  One workgroup per draw: the threads form the terms e_j * r_j of MOM_BS rows at a time,
-// thread 0 adds them in row order (deterministic).  With a diagonal W this is k_moment_objective's w * e * e, bit for bit
-// (the products commute and +0 + x is x).
-__global__ void __launch_bounds__(MOM_BS) k_moment_objective_w(const double *means, const int *counts, int nmom,
-                                                               const double *target, const double *W, double *obj)
+// Quadratic form e' W e of one draw's moments, e = means - target: r_j = sum over the non-zero W_jk in k order of
+// W_jk * e_k, obj = sum over the rows with a non-zero entry in j order of e_j * r_j; NaN if a moment that W touches (row or
+// column) is empty.  W is [nmom x nmom] row-major, or with diag set the [nmom] diagonal of a diagonal matrix: row j then has
+// the one entry W[j] at k = j, and the objective is the weighted sum of squares W_j * e_j * e_j over the non-zero W_j.  One
+// workgroup per draw: the threads form the terms e_j * r_j of MOM_BS rows at a time, thread 0 adds them in row order
+// (deterministic).
+__global__ void __launch_bounds__(MOM_BS) k_moment_objective(const double *means, const int *counts, int nmom,
+                                                             const double *target, const double *W, int diag, double *obj)
 {
     __shared__ double sterm[MOM_BS];
     __shared__ int sflag[MOM_BS];   // bit 0: the row has a non-zero entry, bit 1: it touches an empty moment
@@ -4923,9 +4883,10 @@ __global__ void __launch_bounds__(MOM_BS) k_moment_objective_w(const double *mea
         double term = 0;
         int flag = 0;
         if (j < nmom) {
-            const double *w = W + (size_t)j * nmom;
+            const double *w = diag ? W : W + (size_t)j * nmom;   // (w[k] is W_jk for the k of the loop)
+            const int k0 = diag ? j : 0, k1 = diag ? j + 1 : nmom;
             double r = 0;
-            for (int k = 0; k < nmom; k++) {
+            for (int k = k0; k < k1; k++) {
                 if (w[k] == 0.0) continue;
                 flag |= (c[j] == 0 || c[k] == 0) ? 3 : 1;
                 r += w[k] * (m[k] - target[k]);

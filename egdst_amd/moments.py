@@ -190,7 +190,7 @@ class MomentSpec(list):
 
 
 def objective(means, counts, target, W):
-    """e' W e in the device's order (k_moment_objective_w): e = means - target, r_j = sum over k ascending of the non-zero
+    """e' W e in the device's order (k_moment_objective): e = means - target, r_j = sum over k ascending of the non-zero
     W_jk * e_k, obj = sum over j ascending of e_j * r_j over the rows with a non-zero entry; NaN if a moment W touches is
     empty.  means/counts [nmom] or [ndraw, nmom]; W [nmom, nmom] or a vector (its diagonal)."""
     means, counts = np.asarray(means, dtype=np.float64), np.asarray(counts)

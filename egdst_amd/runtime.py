@@ -117,6 +117,11 @@ class ModelLibrary:
         L.egdst_get_model_info(C.byref(info))
         self.info = info
 
+    @property
+    def nout(self):
+        """columns of a simulated path (egdst_simulate: nsimout)"""
+        return 11 + self.info.nnst + self.info.nnd + self.info.neq
+
     def check(self, rc):
         if rc != 0:
             raise EgdstRuntimeError(rc, (self.lib.egdst_last_error() or b'').decode(errors='replace'))
@@ -481,43 +486,49 @@ class Solver:
             s_, j_ = self._route(draw)
             return s_.simulate_moments(init, randstream, rndtype, j_)
         init = np.asfortranarray(np.atleast_2d(np.asarray(init, dtype=np.float64)))
-        info = self.lib.info
-        nout = 11 + info.nnst + info.nnd + info.neq
-        means = np.zeros((self.nt, nout))
-        counts = np.zeros((self.nt, nout), dtype=np.int32)
+        means = np.zeros((self.nt, self.lib.nout))
+        counts = np.zeros((self.nt, self.lib.nout), dtype=np.int32)
         rs = np.ascontiguousarray(randstream, dtype=np.float64)
         self.lib.check(self.lib.lib.egdst_simulate_moments(self.h, draw, _dp(init), init.shape[0], _dp(rs), rs.size, int(rndtype),
                                                            _dp(means), _ip(counts)))
         return means, counts
+
+    def _estimation_step(self, entry, init, seed, rndtype, randstream_dev, nrand, shape, spec_args, t, w, means_dev, counts_dev,
+                         obj_dev):
+        """What simulate_batch_moments and simulate_batch_spec share: `entry` is the library's function, spec_args what it
+        takes between rndtype and the target, shape the moments of a draw, t / w the host target and weights (None: no
+        objective).  With no device pointers given the results go through torch tensors allocated here and are returned."""
+        init = np.asfortranarray(np.atleast_2d(np.asarray(init, dtype=np.float64)))
+        own = means_dev is None and counts_dev is None and obj_dev is None
+        if own:
+            import torch
+            tm = torch.zeros(self.ndraw, *shape, dtype=torch.float64, device='cuda')
+            tc = torch.zeros(self.ndraw, *shape, dtype=torch.int32, device='cuda')
+            to = torch.zeros(self.ndraw, dtype=torch.float64, device='cuda') if w is not None else None
+            # torch fills them on ITS stream; the library writes them on the handle's: without this the fill may land after the
+            # results (seen once in a few hundred runs: all moments and objectives zero)
+            torch.cuda.current_stream().synchronize()
+            means_dev, counts_dev = tm.data_ptr(), tc.data_ptr()
+            obj_dev = to.data_ptr() if to is not None else None
+        self.lib.check(entry(
+            self.h, _dp(init), init.shape[0], C.c_void_p(randstream_dev) if randstream_dev else None, int(nrand), int(seed),
+            int(rndtype), *spec_args, _dp(t) if t is not None else None, _dp(w) if w is not None else None,
+            C.c_void_p(means_dev) if means_dev else None, C.c_void_p(counts_dev) if counts_dev else None,
+            C.c_void_p(obj_dev) if obj_dev else None))
+        if own:
+            return tm.cpu().numpy(), tc.cpu().numpy(), to.cpu().numpy() if to is not None else None
+        return None
 
     def simulate_batch_moments(self, init, seed=0, rndtype=0, target=None, weight=None, randstream_dev=None, nrand=0,
                                means_dev=None, counts_dev=None, obj_dev=None):
         """egdst_simulate_batch_moments: all draws of the handle, common random numbers; the *_dev arguments are device
         pointers (ints).  With no device pointers given, returns (means [ndraw, nt, nout], counts, objective [ndraw]) through
         torch tensors allocated here."""
-        init = np.asfortranarray(np.atleast_2d(np.asarray(init, dtype=np.float64)))
-        info = self.lib.info
-        nout = 11 + info.nnst + info.nnd + info.neq
-        ncell = nout * self.nt
+        ncell = self.lib.nout * self.nt
         t = np.ascontiguousarray(np.zeros(ncell) if target is None else target, dtype=np.float64).reshape(-1)
         w = np.ascontiguousarray(np.zeros(ncell) if weight is None else weight, dtype=np.float64).reshape(-1)
-        own = means_dev is None and counts_dev is None and obj_dev is None
-        if own:
-            import torch
-            tm = torch.zeros(self.ndraw, self.nt, nout, dtype=torch.float64, device='cuda')
-            tc = torch.zeros(self.ndraw, self.nt, nout, dtype=torch.int32, device='cuda')
-            to = torch.zeros(self.ndraw, dtype=torch.float64, device='cuda')
-            # torch fills them on ITS stream; the library writes them on the handle's: without this the fill may land after the
-            # results (seen once in a few hundred runs: all moments and objectives zero)
-            torch.cuda.current_stream().synchronize()
-            means_dev, counts_dev, obj_dev = tm.data_ptr(), tc.data_ptr(), to.data_ptr()
-        self.lib.check(self.lib.lib.egdst_simulate_batch_moments(
-            self.h, _dp(init), init.shape[0], C.c_void_p(randstream_dev) if randstream_dev else None, int(nrand), int(seed),
-            int(rndtype), _dp(t), _dp(w), C.c_void_p(means_dev) if means_dev else None,
-            C.c_void_p(counts_dev) if counts_dev else None, C.c_void_p(obj_dev) if obj_dev else None))
-        if own:
-            return tm.cpu().numpy(), tc.cpu().numpy(), to.cpu().numpy()
-        return None
+        return self._estimation_step(self.lib.lib.egdst_simulate_batch_moments, init, seed, rndtype, randstream_dev, nrand,
+                                     (self.nt, self.lib.nout), (), t, w, means_dev, counts_dev, obj_dev)
 
     def simulate_batch_spec(self, init, spec, seed=0, rndtype=0, target=None, W=None, randstream_dev=None, nrand=0,
                             means_dev=None, counts_dev=None, obj_dev=None):
@@ -527,7 +538,6 @@ class Solver:
         The *_dev arguments are device pointers (ints); with none given, returns (means [ndraw, nmom], counts [ndraw, nmom],
         objective [ndraw] or None) through torch tensors allocated here."""
         from . import moments
-        init = np.asfortranarray(np.atleast_2d(np.asarray(init, dtype=np.float64)))
         if isinstance(spec, moments.MomentSpec):
             rec = spec.pack(self.nt, layout=self.lib.info)
         else:
@@ -544,24 +554,8 @@ class Solver:
                 w = moments.weight_matrix(W, nmom)
             except ValueError as e:
                 raise EgdstRuntimeError(1, 'simulate_batch_spec: %s' % e) from None
-        own = means_dev is None and counts_dev is None and obj_dev is None
-        if own:
-            import torch
-            tm = torch.zeros(self.ndraw, nmom, dtype=torch.float64, device='cuda')
-            tc = torch.zeros(self.ndraw, nmom, dtype=torch.int32, device='cuda')
-            to = torch.zeros(self.ndraw, dtype=torch.float64, device='cuda') if w is not None else None
-            # torch fills them on ITS stream, the library writes them on the handle's (as in simulate_batch_moments)
-            torch.cuda.current_stream().synchronize()
-            means_dev, counts_dev = tm.data_ptr(), tc.data_ptr()
-            obj_dev = to.data_ptr() if to is not None else None
-        self.lib.check(self.lib.lib.egdst_simulate_batch_spec(
-            self.h, _dp(init), init.shape[0], C.c_void_p(randstream_dev) if randstream_dev else None, int(nrand), int(seed),
-            int(rndtype), rec.ctypes.data_as(C.c_void_p), nmom, _dp(t) if t is not None else None,
-            _dp(w) if w is not None else None, C.c_void_p(means_dev) if means_dev else None,
-            C.c_void_p(counts_dev) if counts_dev else None, C.c_void_p(obj_dev) if obj_dev else None))
-        if own:
-            return tm.cpu().numpy(), tc.cpu().numpy(), to.cpu().numpy() if to is not None else None
-        return None
+        return self._estimation_step(self.lib.lib.egdst_simulate_batch_spec, init, seed, rndtype, randstream_dev, nrand,
+                                     (nmom,), (rec.ctypes.data_as(C.c_void_p), nmom), t, w, means_dev, counts_dev, obj_dev)
 
     def call(self, sw, args, draw=0):
         """egdst_call gateway (egdst_call.c:17-164): sw 1 utility, 2 marginal utility, 3 discount, 4 budget, 5 marginal
@@ -580,9 +574,7 @@ class Solver:
             return s_.simulate(init, randstream, rndtype, j_)
         init = np.asfortranarray(np.atleast_2d(np.asarray(init, dtype=np.float64)))
         nsim = init.shape[0]
-        info = self.lib.info
-        nout = 11 + info.nnst + info.nnd + info.neq
-        sims = np.zeros((nsim, self.nt, nout))  # C order == column-major [nout x nt x nsim]
+        sims = np.zeros((nsim, self.nt, self.lib.nout))  # C order == column-major [nout x nt x nsim]
         rs = np.ascontiguousarray(randstream, dtype=np.float64)
         self.lib.check(self.lib.lib.egdst_simulate(self.h, draw, _dp(init), nsim, _dp(rs), rs.size, int(rndtype),
                                                    _dp(sims)))

@@ -1,6 +1,8 @@
 """The estimation step with user-defined moments and a full weighting matrix on the device (egdst_simulate_batch_spec):
 the same bits as egdst_simulate_batch_moments where the two overlap, the oracle's paths reduced by MomentSpec.evaluate with
 the device's summation order, several slices of draws, and malformed records."""
+import functools
+
 import numpy as np
 import pytest
 import torch  # noqa: F401  (first: the model libraries then bind torch's HIP runtime, which the result tensors need)
@@ -21,8 +23,7 @@ def bits_equal(a, b):
 
 
 def _nout(s):
-    i = s.lib.info
-    return 11 + i.nnst + i.nnd + i.neq
+    return s.lib.nout
 
 
 def _per_period(s, cols=None):
@@ -32,13 +33,23 @@ def _per_period(s, cols=None):
     return mo.MomentSpec([mo.mean(c, periods=it) for it in range(s.nt) for c in cols], layout=s)
 
 
+@functools.lru_cache(maxsize=None)
+def _c2_case():
+    """C2 setup of test_estimation_step_on_device, solved once on the device and once by the oracle"""
+    m, gen = workloads.c2(a0=0, ngridm=300, T=30)
+    P = gen(1024)[[0, 1, 2, 3, 5, 8, 13, 771]]
+    orc = Oracle(m)
+    return m, P, gpu_solve(m, P), orc, [orc.solve(p) for p in P]
+
+
 @pytest.mark.parametrize('rndtype', [0, 1])
 def test_per_period_spec_is_the_batch_moments_path(rndtype):
     """C2 setup of test_estimation_step_on_device: means, counts and the objective with a diagonal W bit-identical to
-    simulate_batch_moments; the failing draws give NaN / 0 / NaN."""
-    m, gen = workloads.c2(a0=0, ngridm=300, T=30)
-    P = gen(1024)[[0, 1, 2, 3, 5, 8, 13, 771]]
-    s = gpu_solve(m, P)
+    simulate_batch_moments; the failing draws give NaN / 0 / NaN.  The two are doors of one kernel, so simulate_batch_moments is
+    pinned by itself as well: for every draw (the oracle solves all eight) bit-identical to the per-period spec evaluated in
+    the device's order on the oracle's paths for the host replay of the uniforms, and to moments.objective with the weights as
+    a diagonal; 420 cells, so the objective kernel crosses a boundary of its 256-row chunks."""
+    m, P, s, orc, sols = _c2_case()
     st = s.status()[0]
     rng = np.random.default_rng(5)
     nsim = 2000
@@ -59,6 +70,15 @@ def test_per_period_spec_is_the_batch_moments_path(rndtype):
     for d in np.nonzero(st)[0]:
         assert np.isnan(sm[d]).all() and not sc[d].any() and np.isnan(so[d])
     assert np.isfinite(so[st == 0]).all()
+    assert s.nt * nout > 256
+    rs = estimation_case.uniforms(seed, 4 * s.nt * (1 if rndtype == 1 else nsim))
+    for d in range(s.ndraw):
+        assert sols[d].rc == 0 and st[d] == 0, (d, sols[d].rc, st[d])
+        rm, rc = spec.evaluate(orc.sim(sols[d], init, rs, rndtype=rndtype, params=P[d]), block=256)
+        assert np.array_equal(bc[d].reshape(-1), rc), (rndtype, d)
+        assert bits_equal(bm[d].reshape(-1), rm), (rndtype, d)
+        ro = mo.objective(rm, rc, target.reshape(-1), weight.reshape(-1))
+        assert bits_equal(bo[d], ro), (rndtype, d, bo[d], ro)
 
 
 def _full_spec(m, nt, nch):
@@ -158,3 +178,45 @@ def test_malformed_spec_is_refused_and_the_handle_stays_usable():
         s.simulate_batch_spec(init, mo.MomentSpec([mo.mean('C', periods=s.nt)]), seed=1)
     again = s.simulate_batch_spec(init, spec, seed=1)
     assert bits_equal(again[0], good[0]) and np.array_equal(again[1], good[1])
+
+
+def test_diagonal_weights_of_the_batch_moments_path():
+    """The weight vector of simulate_batch_moments is the diagonal of W: retirement2, one draw, 300 agents of whom some
+    start outside [a0, mmax] and have no value anywhere (on the oracle's paths 260 of the 300 count in every cell that has
+    a value; columns 6, 7, 8 and 13 have none in the first period), and the same agents all started above mmax, which
+    empties every cell, those of the last period included.  All weights zero: exactly 0.0 whatever is empty; a weight on an
+    empty cell: NaN; a weight on a populated cell: w * e * e in the order of the contract, e = mean - target, from the
+    returned mean; and np.diag of each vector through simulate_batch_spec with the per-period spec: the same bits."""
+    m = examples.retirement2()
+    s = gpu_solve(m, m.param_vector()[None])
+    nsim, nout = 300, _nout(s)
+    ncell = s.nt * nout
+    spec = _per_period(s)
+    target = np.random.default_rng(17).uniform(0, 2, ncell)
+    x = np.random.default_rng(2).uniform(m.a0 - 1, m.mmax + 1, nsim)
+    mixed = np.column_stack([np.ones(nsim), x])
+    outside = np.column_stack([np.ones(nsim), m.mmax + 1 + np.abs(x)])
+
+    def both_doors(init, w):
+        means, counts, obj = s.simulate_batch_moments(init, seed=31, target=target, weight=w)
+        sm, sc, so = s.simulate_batch_spec(init, spec, seed=31, target=target, W=np.diag(w))
+        assert np.array_equal(sc, counts.reshape(1, -1)) and bits_equal(sm, means.reshape(1, -1)) and bits_equal(so, obj)
+        return means.reshape(-1), counts.reshape(-1), obj[0]
+
+    zero = np.zeros(ncell)
+    means, counts, obj = both_doors(mixed, zero)
+    assert (counts == 0).any() and (counts[-nout:] > 0).all() and 0 < counts.max() < nsim
+    assert obj == 0.0 and not np.signbit(obj)
+    empty, full = int(np.nonzero(counts == 0)[0][-1]), ncell - nout + 1   # (consumption in the last period)
+    w = zero.copy()
+    w[empty] = 3.0
+    assert np.isnan(both_doors(mixed, w)[2])
+    w = zero.copy()
+    w[full] = 3.0
+    e = means[full] - target[full]
+    assert bits_equal(both_doors(mixed, w)[2], w[full] * e * e) and e != 0.0
+
+    means, counts, obj = both_doors(outside, zero)
+    assert not counts.any() and np.isnan(means).all()
+    assert obj == 0.0 and not np.signbit(obj)
+    assert np.isnan(both_doors(outside, w)[2])

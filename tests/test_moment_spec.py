@@ -157,7 +157,7 @@ def test_objective_order_and_empty_moments():
     w[2] = 0
     e = means - target
     acc = 0.0
-    for k in range(n):   # k_moment_objective: weight * e * e in cell order
+    for k in range(n):   # k_moment_objective with a diagonal: weight * e * e in cell order
         if w[k] != 0:
             acc += w[k] * e[k] * e[k]
     assert mo.objective(means, counts, target, w) == acc      # a vector is the diagonal: the same bits
