@@ -83,7 +83,13 @@ const char *egdst_last_error(void);
 
 /* Create a batch of `ndraw` independent solves of this model.  keep_history=1 keeps every period's
  * tables resident (needed for cell export and simulation); 0 keeps two ping-pong periods only.
- * stream: a hipStream_t (NULL = the library creates its own non-blocking stream). */
+ * stream: a hipStream_t (NULL = the library creates its own non-blocking stream, and destroys it with the handle).
+ * EGDST_STREAM_PER_THREAD is HIP's hipStreamPerThread for hosts that do not include the HIP headers: the calling thread's
+ * own default stream, which lives as long as the process.  A host that creates and destroys a handle per call (the MEX
+ * shims) should pass it: a stream of the handle's own is a new stream per call, the runtime may put it on another hardware
+ * queue than the last one, and a queue on which the solver's kernels run first gets scratch memory of its own (56 MiB on
+ * an MI355X, kept until the process ends). */
+#define EGDST_STREAM_PER_THREAD ((void *)2)
 int egdst_create(const egdst_desc *desc, int ndraw, int keep_history, void *stream, egdst_handle **out);
 /* The same with PHYSICAL row capacity rows_cap < ngridmax for every device list and table (0 = exact).  The
  * reference sizes each cell for ngridmax rows (egdst_solver.c:198-217) although a solved cell holds about ngridm;

@@ -3,7 +3,8 @@
  * Replaces @egdstmodel/egdst_solver.c:143-239 (mexFunction); called by egdstmodel.solve, egdstmodel.m:1170.
  * Same argument counts, same outputs: M and D are nst x nt cell arrays in saveoutput's layout (egdst_solver.c:917-952),
  * dbgout the (nt*nst*nd*2*nt) x 7 kink log (:178-181, 1866-1879).  Errors of the solver do not throw: warning + partially
- * filled cells (:237).
+ * filled cells (:237).  The warning is the solver's own message, as the reference's `err` is: egdst_strerror of the draw's
+ * status, without the "draw 0:" that egdst_last_error puts in front of it for batches.
  */
 #include "egdst_shim_common.h"
 
@@ -14,6 +15,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     egdst_desc d;
     egdst_handle *h;
     mwSize dims[2];
+    const char *msg = NULL;
     int it, ist, nt, rc, nrow;
 
     if (nrhs != 1) mexErrMsgTxt("Error: wrong number of inputs!");
@@ -26,6 +28,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     if (!h) mexErrMsgTxt(egdst_last_error());
     egdst_set_dbgout(h, 1); /* keep the kink log: third output */
     rc = egdst_solve(h);
+    if (rc) msg = rc >= EGDST_E_INTERP2 && rc < EGDST_E_NOT_SOLVED ? egdst_strerror(rc) : egdst_last_error();
 
     dims[0] = (mwSize)info.nst;
     dims[1] = (mwSize)nt;
@@ -47,6 +50,6 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[])
     nrow = nt * info.nst * info.nd * 2 * nt;
     plhs[2] = mxCreateDoubleMatrix((mwSize)nrow, 7, mxREAL);
     egdst_get_dbgout(h, 0, mxGetPr(plhs[2]), NULL);
-    if (rc) mexWarnMsgTxt(egdst_last_error());
+    if (rc) mexWarnMsgTxt(msg);
     egdst_destroy(h);
 }

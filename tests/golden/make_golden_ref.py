@@ -6,7 +6,9 @@ Needs the reference sources (EGDST_REFERENCE_DIR).  Data only: what the referenc
 
   ref_<model>.npz      the twelve example models and C5 at T=10, ngridm=200: descriptor, parameters, len/thlen, the rows of
                        M, C, A, V and of D, TH of all cells back to back (cell order: it up, ist up), dbgout rows, the
-                       simulator's panels for both rndtype with their init / randstream, the accessor's results case by case
+                       simulator's panels for both rndtype with their init / randstream, the accessor's results case by case;
+                       the warnings of every simulator and accessor call (count and text), and two accessor calls with a
+                       wrong column count (xcall<k>_*)
   ref_C2_draws.npz     the first 256 C2 draws of the bench at a0=-5 and at a0=0: parameters, which draws fail, at which cell,
                        with which text; len/thlen of every draw and one checksum per draw
   ref_big_<case>.npz   C1, C2, C2_a0m5, C3, C4 at full size in the layout of big_*.npz (per-cell index-weighted checksums)
@@ -62,6 +64,13 @@ def recorded_call_cases(m, nt):
     return out
 
 
+def wrong_column_cases(m):
+    """Accessor calls whose argument matrix has the wrong number of columns: utility without consumption, value function
+    without cash.  The reference warns once and leaves zeros."""
+    it, ist = np.full(5, float(m.t0)), np.ones(5)
+    return [(1, np.column_stack([it, ist, np.ones(5)])), (6, np.column_stack([it, ist]))]
+
+
 def flat(sol):
     """Rows of all cells back to back."""
     nt, nst = sol.len.shape
@@ -108,12 +117,19 @@ def model_arrays(name):
         r = R.sim(sol, init, rs, rt)
         assert r.err == '' and r.sims is not None
         out['sims%d' % rt] = r.sims
+        out['sims%d_nwarn' % rt], out['sims%d_warnings' % rt] = np.int64(r.nwarn), np.array(r.warnings)
     cases = recorded_call_cases(m, sol.nt)
     out['ncall'] = np.int64(len(cases))
     for k, (sw, args) in enumerate(cases):
         r = R.call(sol, sw, args)
         assert r.err == '' and r.res is not None
         out['call%d_sw' % k], out['call%d_args' % k], out['call%d_res' % k] = np.int64(sw), args, r.res
+        out['call%d_nwarn' % k], out['call%d_warnings' % k] = np.int64(r.nwarn), np.array(r.warnings)
+    for k, (sw, args) in enumerate(wrong_column_cases(m)):
+        r = R.call(sol, sw, args)
+        assert r.err == '' and r.res is not None
+        out['xcall%d_sw' % k], out['xcall%d_args' % k], out['xcall%d_res' % k] = np.int64(sw), args, r.res
+        out['xcall%d_nwarn' % k], out['xcall%d_warnings' % k] = np.int64(r.nwarn), np.array(r.warnings)
     return out
 
 

@@ -20,10 +20,8 @@ sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 import build_ref  # noqa: E402
 from oracle_harness import OracleSolution  # noqa: E402
 
-P = C.c_void_p
-SCALARS = ('t0', 'T', 'ngridm', 'ngridmax', 'nthrhmax', 'ny', 'nd', 'nnd', 'nst', 'nnst', 'mmax', 'a0')
-PROPS = SCALARS + ('stm', 'states', 'decisions', 'optim', 'quadrature', 'param', 's', 'eq', 'init', 'randstream', 'M', 'D')
-OPTIM = ('optim_UasD', 'optim_MUnoD', 'optim_UnoD', 'optim_TRPRnoSH')
+import mex_object  # noqa: E402
+from mex_object import Host as _Host, P, SCALARS, PROPS, OPTIM  # noqa: E402,F401
 
 
 class ReferenceUnavailable(Exception):
@@ -39,64 +37,6 @@ def available(model=None):
     if build_ref.reference_dir() is not None:
         return True
     return model is not None and build_ref.find(model) is not None
-
-
-class _Host:
-    """One of the three libraries with the Matrix API typed for ctypes."""
-
-    def __init__(self, path):
-        lib = self.lib = C.CDLL(path)
-        sz = C.c_size_t
-        for name, res, args in (
-                ('mxCreateDoubleMatrix', P, [sz, sz, C.c_int]), ('mxCreateDoubleScalar', P, [C.c_double]),
-                ('mxCreateNumericArray', P, [sz, C.POINTER(sz), C.c_int, C.c_int]),
-                ('mxCreateCellMatrix', P, [sz, sz]), ('mxCreateStructMatrix', P, [sz, sz, C.c_int, C.POINTER(C.c_char_p)]),
-                ('mxCreateLogicalScalar', P, [C.c_bool]), ('mxGetPr', C.POINTER(C.c_double), [P]), ('mxGetM', sz, [P]),
-                ('mxGetN', sz, [P]), ('mxGetNumberOfElements', sz, [P]), ('mxGetCell', P, [P, sz]),
-                ('mxSetCell', None, [P, sz, P]), ('mxSetField', None, [P, sz, C.c_char_p, P]),
-                ('ref_run', C.c_int, [C.c_int, C.POINTER(P), C.c_int, C.POINTER(P), C.c_char_p, sz]),
-                ('ref_warnings', C.c_char_p, []), ('ref_warning_count', sz, []), ('ref_reset_warnings', None, [])):
-            f = getattr(lib, name)
-            f.restype, f.argtypes = res, args
-
-    def double(self, a):
-        a = np.asarray(a, dtype=np.float64)
-        if a.ndim == 0:
-            a = a.reshape(1, 1)
-        elif a.ndim == 1:
-            a = a.reshape(-1, 1)
-        mx = self.lib.mxCreateDoubleMatrix(a.shape[0], a.shape[1], 0)
-        if a.size:
-            flat = np.asfortranarray(a).reshape(-1, order='F')
-            C.memmove(self.lib.mxGetPr(mx), flat.ctypes.data, flat.nbytes)
-        return mx
-
-    def struct(self, n, fields):
-        names = (C.c_char_p * len(fields))(*[f.encode() for f in fields])
-        return self.lib.mxCreateStructMatrix(1, n, len(fields), names)
-
-    def array(self, mx):
-        """Copy of a real double matrix as [rows x cols]."""
-        m, n = self.lib.mxGetM(mx), self.lib.mxGetN(mx)
-        if m * n == 0:
-            return np.zeros((m, n))
-        return np.ctypeslib.as_array(self.lib.mxGetPr(mx), shape=(m * n,)).copy().reshape((m, n), order='F')
-
-    def cells(self, arrays):
-        mx = self.lib.mxCreateCellMatrix(len(arrays), 1)
-        for i, a in enumerate(arrays):
-            if a is not None:
-                self.lib.mxSetCell(mx, i, self.double(a))
-        return mx
-
-    def run(self, nlhs, prhs):
-        plhs = (P * max(nlhs, 1))()
-        rhs = (P * len(prhs))(*prhs)
-        buf = C.create_string_buffer(2048)
-        self.lib.ref_reset_warnings()
-        rc = self.lib.ref_run(nlhs, plhs, len(prhs), rhs, buf, len(buf))
-        warn = (self.lib.ref_warnings() or b'').decode(errors='replace')
-        return rc, list(plhs), buf.value.decode(errors='replace'), warn, int(self.lib.ref_warning_count())
 
 
 def _in_child(fn):
@@ -161,50 +101,8 @@ class Reference:
 
     # ------------------------------------------------------------------ the Model object
     def _model(self, h, params=None, sol=None, init=None, randstream=None):
-        m = self.model
-        d = m.descriptor()
-        optim = m.analyse_optim()
-        par = m.param_vector() if params is None else np.asarray(params, dtype=np.float64)
-        obj = h.struct(1, PROPS)
-        put = lambda k, v: h.lib.mxSetField(obj, 0, k.encode(), v)   # noqa: E731
-        for k in SCALARS:
-            put(k, h.double(float(d[k]) if k in d else float(getattr(m, k))))
-        put('stm', h.double(np.asarray(m.stm, dtype=float).reshape(1, -1)))
-        put('states', h.double(np.asarray(m.states, dtype=float)))
-        put('decisions', h.double(np.asarray(m.decisions, dtype=float)))
-        put('quadrature', h.double(np.asarray(d['quadrature'], dtype=float).reshape(2, -1).T))
-        o = h.struct(1, OPTIM)
-        for k in OPTIM:
-            h.lib.mxSetField(o, 0, k.encode(), h.lib.mxCreateLogicalScalar(bool(optim[k])))
-        put('optim', o)
-        if len(par):
-            ps = h.struct(len(par), ('value',))
-            for i, v in enumerate(par):
-                h.lib.mxSetField(ps, i, b'value', h.lib.mxCreateDoubleScalar(float(v)))
-            put('param', ps)
-        ss = h.struct(len(m.s), ('discrete', 'grid'))
-        for i, v in enumerate(m.s):
-            h.lib.mxSetField(ss, i, b'discrete', h.lib.mxCreateLogicalScalar(v.type == 'discrete'))
-            h.lib.mxSetField(ss, i, b'grid', h.double(np.asarray(v.values if v.type == 'continuous' else [], dtype=float)))
-        put('s', ss)
-        put('eq', h.struct(len(m.eq), ('ref',)))
-        if init is not None:
-            put('init', h.double(np.atleast_2d(np.asarray(init, dtype=float))))
-        if randstream is not None:
-            put('randstream', h.double(np.asarray(randstream, dtype=float)))
-        if sol is not None:
-            Mc, Dc = [], []
-            for it in range(sol.nt):             # cell index ist + it*nst
-                for ist in range(sol.nst):
-                    if sol.len[it, ist] > 0:
-                        Mc.append(sol.cell_M(it, ist))
-                        Dc.append(sol.cell_D(it, ist))
-                    else:
-                        Mc.append(None)
-                        Dc.append(None)
-            put('M', h.cells(Mc))
-            put('D', h.cells(Dc))
-        return obj
+        """tests/mex_object.py: the same properties, built by the same code, as the shims get (tests/shim_harness.py)."""
+        return mex_object.build_object(h, mex_object.properties(self.model, params, sol, init, randstream))
 
     # ------------------------------------------------------------------ gateways
     def solve(self, params=None, dbgout=False):

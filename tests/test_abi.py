@@ -23,6 +23,17 @@ def test_header_symbols_are_exported(lib):
         assert hasattr(lib.lib, s)
 
 
+def test_stream_per_thread_is_the_runtimes_own_constant():
+    """EGDST_STREAM_PER_THREAD lets a host without the HIP headers name hipStreamPerThread: egdst_create casts the stream it
+    is given to hipStream_t, so the header's value must be the one of the HIP headers the library is compiled with."""
+    import shim_harness
+    hdr = open(os.path.join(ROOT, 'include', 'egdst.h')).read()
+    ours = re.search(r'^#define EGDST_STREAM_PER_THREAD \(\(void \*\)(\d+)\)$', hdr, flags=re.M)
+    hip = open(os.path.join(os.environ.get('ROCM_PATH', '/opt/rocm'), 'include', 'hip', 'hip_runtime_api.h')).read()
+    theirs = re.search(r'^#define hipStreamPerThread \(\(hipStream_t\)(\d+)\)$', hip, flags=re.M)
+    assert ours and theirs and int(ours.group(1)) == int(theirs.group(1)) == shim_harness.STREAM_PER_THREAD
+
+
 def test_model_info_and_error_texts(lib):
     i = lib.info
     assert (i.nst, i.nd, i.nparam, i.neq, i.distrib) == (1, 1, 2, 1, 1)

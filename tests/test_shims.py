@@ -1,8 +1,8 @@
 """The MEX shim sources (shims/*.c: the reference-side bindings of the three gateways, egdst_solver.c:143, egdst_simulator.c:47,
 egdst_call.c:17) are held to the MEX C API's types and to include/egdst.h by the compiler: gcc -fsyntax-only -Wall -Wextra
 -Werror against a DECLARATIONS-ONLY mex.h (tests/mex_decls).  An undefined identifier, a wrong argument count or a pointer
-mismatch in a shim fails here.  No MATLAB exists in the image, so nothing is linked; the sequence of library calls the shims
-make (create, set_params, set_cell_M/D, simulate / call, destroy) runs on the GPU in tests/test_gpu_parity.py::test_import_*."""
+mismatch in a shim fails here.  These are the checks on the TEXT of the shims; the shims are linked and run, against the MEX
+host of oracle/mexhost/, in tests/test_shims_run.py (CPU harness library) and tests/test_gpu_shims.py (MI355X)."""
 import glob
 import os
 import re
