@@ -1413,7 +1413,8 @@ extern "C" double egdst_uniform(unsigned long long seed, unsigned long long k) {
 #endif
 // The estimation step on the device, behind egdst_simulate_batch_moments and egdst_simulate_batch_spec (which check their
 // arguments): every draw of the handle is simulated with the same agents and the same uniforms (common random numbers),
-// k_moments reduces the paths to nmom moments per draw and k_moment_objective forms the draw's distance to the target.
+// k_moments reduces the paths to nmom moments per draw (k_quantiles those that are quantiles, launched only for a spec that has
+// one) and k_moment_objective forms the draw's distance to the target.
 // spec == nullptr: the moments are the nmom = EG_NOUT * nt per-period cells and W [nmom] is the diagonal of the weighting;
 // otherwise spec [nmom] (host) and W [nmom x nmom].  Draws [d0, d0+nd) are simulated together as long as their paths fit
 // EG_SIM_SLICE_BYTES, and a slice is reduced on the handle's stream before the next one overwrites the paths
@@ -1435,6 +1436,12 @@ static int estimation_step(egdst_handle *h, const double *init, int nsim, const 
         HIPCHK(hipMemcpyAsync(h->sim_tgt, target, sizeof(double) * (size_t)nmom, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->sim_W, W, sizeof(double) * nW, hipMemcpyHostToDevice, h->stream));
     }
+    int q_first = 0, q_last = -1;   // the records [q_first, q_last] hold every quantile (kind 3) of the spec: k_quantiles' grid
+    for (int j = 0; spec && j < nmom; j++)
+        if (spec[j].kind == 3) {
+            if (q_last < 0) q_first = j;
+            q_last = j;
+        }
     const size_t per_draw = sizeof(double) * (size_t)EG_NOUT * g.nt * nsim;
     int slice = (int)(EG_SIM_SLICE_BYTES / (per_draw ? per_draw : 1));
     if (slice < 1) slice = 1;
@@ -1446,6 +1453,10 @@ static int estimation_step(egdst_handle *h, const double *init, int nsim, const 
         hipLaunchKernelGGL(k_moments, dim3(nmom, nd), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_sims, nsim, g.nt,
                            spec ? (const egdst_moment *)h->sim_spec : nullptr, nmom, h->sim_means + (size_t)d0 * nmom,
                            h->sim_counts + (size_t)d0 * nmom);
+        if (q_last >= q_first)   // the quantile records, which k_moments leaves alone
+            hipLaunchKernelGGL(k_quantiles, dim3(q_last - q_first + 1, nd), dim3(QNT_BS), 0, h->stream, (const double *)h->sim_sims,
+                               nsim, g.nt, (const egdst_moment *)h->sim_spec, q_first, nmom, h->sim_means + (size_t)d0 * nmom,
+                               h->sim_counts + (size_t)d0 * nmom);
     }
     if (obj_dev)
         hipLaunchKernelGGL(k_moment_objective, dim3(g.ndraw), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_means,
@@ -1486,7 +1497,8 @@ extern "C" int egdst_simulate_batch_spec(egdst_handle *h, const double *init, in
     for (int j = 0; j < nmom; j++) {
         const egdst_moment &q = spec[j];
         const char *bad = nullptr;
-        if (q.kind < 0 || q.kind > 2) bad = "kind is not 0, 1 or 2";
+        if (q.kind < 0 || q.kind > 3) bad = "kind is not 0, 1, 2 or 3";
+        else if (q.kind == 3 && !(q.lo > 0.0 && q.lo < 1.0)) bad = "the p of a quantile (lo) is not inside (0, 1)";   // (NaN fails both)
         else if (q.col < 0 || q.col >= nout) bad = "col is outside the simulated columns";
         else if (q.col2 < 0 || q.col2 >= nout) bad = "col2 is outside the simulated columns";
         else if (q.cond_col < -1 || q.cond_col >= nout) bad = "cond_col is outside the simulated columns";
@@ -1718,6 +1730,54 @@ extern "C" int egdst_math_eval(int fn, int n, const double *x, const double *y, 
     if (e == hipSuccess) e = hipMemcpy(out, d + nx + ny, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (e != hipSuccess) return set_err(EGDST_E_HIP, "egdst_math_eval: %s", hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int egdst_quantile_lds_keys(void) { return QNT_LDS_KEYS; }
+
+// The selection of k_quantiles on caller-supplied values (diagnostics): x becomes column 0 of an [n][1][EG_NOUT] panel whose
+// other columns are NaN, p[i] the kind-3 record i over that one period, and the kernel runs as in the estimation step.
+extern "C" int egdst_quantile_eval(int n, const double *x, int np, const double *p, double *out, int *count)
+{
+    if (n < 1 || np < 1 || !x || !p || !out || !count) return set_err(EGDST_E_ARG, "egdst_quantile_eval: bad arguments");
+    for (int i = 0; i < np; i++)
+        if (!(p[i] > 0.0 && p[i] < 1.0)) return set_err(EGDST_E_ARG, "egdst_quantile_eval: p[%d] is not inside (0, 1)", i);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_err(EGDST_E_NOGPU, "%s", egdst_strerror(EGDST_E_NOGPU));
+    const size_t npanel = (size_t)n * EG_NOUT;
+    double *panel = (double *)malloc(sizeof(double) * npanel);
+    egdst_moment *rec = (egdst_moment *)calloc((size_t)np, sizeof(egdst_moment));
+    int *cnt = (int *)malloc(sizeof(int) * (size_t)np);
+    double *d_panel = nullptr, *d_means = nullptr;
+    egdst_moment *d_rec = nullptr;
+    int *d_cnt = nullptr;
+    if (!panel || !rec || !cnt) {
+        free(panel), free(rec), free(cnt);
+        return set_err(EGDST_E_HIP, "egdst_quantile_eval: out of host memory");
+    }
+    for (size_t i = 0; i < npanel; i++) panel[i] = NAN;
+    for (int i = 0; i < n; i++) panel[(size_t)i * EG_NOUT] = x[i];
+    for (int i = 0; i < np; i++) rec[i].kind = 3, rec[i].cond_col = -1, rec[i].lo = p[i];
+    hipError_t e = hipMalloc(&d_panel, sizeof(double) * npanel);
+    if (e == hipSuccess) e = hipMalloc(&d_rec, sizeof(egdst_moment) * (size_t)np);
+    if (e == hipSuccess) e = hipMalloc(&d_means, sizeof(double) * (size_t)np);
+    if (e == hipSuccess) e = hipMalloc(&d_cnt, sizeof(int) * (size_t)np);
+    if (e == hipSuccess) e = hipMemcpy(d_panel, panel, sizeof(double) * npanel, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rec, rec, sizeof(egdst_moment) * (size_t)np, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_quantiles, dim3(np), dim3(QNT_BS), 0, 0, (const double *)d_panel, n, 1, (const egdst_moment *)d_rec, 0, np,
+                           d_means, d_cnt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_means, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(cnt, d_cnt, sizeof(int) * (size_t)np, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) *count = cnt[0];   // (the records share the column and the period: one count)
+    if (d_panel) (void)hipFree(d_panel);
+    if (d_rec) (void)hipFree(d_rec);
+    if (d_means) (void)hipFree(d_means);
+    if (d_cnt) (void)hipFree(d_cnt);
+    free(panel), free(rec), free(cnt);
+    if (e != hipSuccess) return set_err(EGDST_E_HIP, "egdst_quantile_eval: %s", hipGetErrorString(e));
     return 0;
 }
 

@@ -4822,6 +4822,7 @@ __global__ void __launch_bounds__(MOM_BS) k_moments(const double *sims, int nsim
     __shared__ int scnt[MOM_BS];
     const int j = blockIdx.x, tid = threadIdx.x;
     const egdst_moment q = spec ? spec[j] : eg_cell_moment(j);
+    if (q.kind == 3) return;   // (a quantile: k_quantiles writes it; the whole workgroup leaves, ahead of every barrier)
     const size_t per_agent = (size_t)EG_NOUT * nt;
     sims += (size_t)blockIdx.y * per_agent * nsim;   // (one set of paths, means and counts per draw of the launch)
     means += (size_t)blockIdx.y * nmom;
@@ -4859,6 +4860,123 @@ __global__ void __launch_bounds__(MOM_BS) k_moments(const double *sims, int nsim
     if (tid == 0) {
         counts[j] = scnt[0];
         means[j] = scnt[0] ? ssum[0] / scnt[0] : NAN;
+    }
+}
+
+// Candidates (agent, period pairs of a record's period range) up to which a quantile's keys are gathered into LDS once; beyond,
+// every pass of the selection reads the column again.  2048 keys are 16 KiB, 17.1 KiB with the histogram: eight workgroups of
+// four waves share a CU (137 of its 160 KiB, and the 32 waves a CU holds), and the 2000 agents of a per-period quantile fit.
+#ifndef QNT_LDS_KEYS
+#define QNT_LDS_KEYS 2048
+#endif
+#ifdef EGDST_EMU
+#define QNT_BS 1
+#else
+#define QNT_BS 256
+#endif
+static_assert(QNT_LDS_KEYS >= 1 && QNT_LDS_KEYS <= 16384, "the keys of a quantile must fit the LDS of a CU beside the histogram");
+
+// The order of the quantiles (include/egdst.h): the keys compare as unsigned integers the way the values compare, with
+// -0.0 before +0.0.  No qualifying value has key 0 (that is a NaN), which marks a pair that does not qualify.
+static __device__ __forceinline__ unsigned long long qnt_key(unsigned long long u)
+{
+    return (u >> 63) ? ~u : (u | (1ull << 63));
+}
+
+// Key of candidate c of record q: agent c / np, period it_first + c % np (np periods); 0 if the pair does not qualify.
+static __device__ __forceinline__ unsigned long long qnt_candidate(const double *sims, size_t per_agent, const egdst_moment &q,
+                                                                   int np, int c)
+{
+    const double *o = sims + (size_t)(c / np) * per_agent + (size_t)(q.it_first + c % np) * EG_NOUT;
+    const unsigned long long u = egm_bits(o[q.col]);
+    if ((u & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) return 0;   // NaN
+    if (q.cond_col >= 0) {
+        const double cv = o[q.cond_col];
+        if (!(cv >= q.cond_lo && cv <= q.cond_hi)) return 0;   // (NaN fails both)
+    }
+    return qnt_key(u);
+}
+
+// Quantile moments (kind 3 of egdst_moment, include/egdst.h) of one draw's simulated paths by exact selection: one workgroup
+// per (record j0 + blockIdx.x, draw of the launch); records of another kind leave at once.  Most-significant-digit radix
+// select on the 64-bit keys: pass d counts, in a 256-bin histogram, byte 7 - d of the keys that agree with the digits
+// selected so far, the bin that holds rank k becomes the next digit and k the rank inside it; after eight passes the digits
+// are the key.  Only integers are added, so the result does not depend on scheduling.  A record with at most QNT_LDS_KEYS
+// candidates (nsim times its periods) gathers its keys into LDS once -- a column read is strided by EG_NOUT doubles -- the
+// others read the column in every pass.  Every loop with a barrier has workgroup-uniform bounds; what one thread decides
+// (n, the bin, the new k) goes through LDS and a barrier.
+__global__ void __launch_bounds__(QNT_BS) k_quantiles(const double *sims, int nsim, int nt, const egdst_moment *spec, int j0,
+                                                      int nmom, double *means, int *counts)
+{
+    __shared__ unsigned long long skey[QNT_LDS_KEYS];
+    __shared__ unsigned shist[256];
+    __shared__ unsigned sgrp[16];   // sums of 16 bins each
+    __shared__ unsigned ssel[3];    // selected bin, rank inside it, n
+    const int j = j0 + blockIdx.x, tid = threadIdx.x;
+    const egdst_moment q = spec[j];
+    if (q.kind != 3) return;   // (the whole workgroup, ahead of every barrier)
+    const size_t per_agent = (size_t)EG_NOUT * nt;
+    sims += (size_t)blockIdx.y * per_agent * nsim;
+    means += (size_t)blockIdx.y * nmom;
+    counts += (size_t)blockIdx.y * nmom;
+    const int np = q.it_last - q.it_first + 1, ncand = nsim * np;   // (the host checked that the product fits an int)
+    const bool in_lds = ncand <= QNT_LDS_KEYS;
+    if (in_lds)
+        for (int c = tid; c < ncand; c += QNT_BS) skey[c] = qnt_candidate(sims, per_agent, q, np, c);
+    unsigned long long prefix = 0, mask = 0;   // the digits selected so far, and the bits they occupy
+    for (int pass = 0; pass < 8; pass++) {
+        const int shift = 56 - 8 * pass;
+        for (int b = tid; b < 256; b += QNT_BS) shist[b] = 0;
+        __syncthreads();   // (also: the gathered keys are in LDS)
+        for (int c = tid; c < ncand; c += QNT_BS) {
+            const unsigned long long key = in_lds ? skey[c] : qnt_candidate(sims, per_agent, q, np, c);
+            if (key != 0 && (key & mask) == prefix) atomicAdd(&shist[(unsigned)(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        for (int g = tid; g < 16; g += QNT_BS) {
+            unsigned s = 0;
+            for (int i = 0; i < 16; i++) s += shist[16 * g + i];
+            sgrp[g] = s;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned k;
+            if (pass == 0) {   // the histogram of the first digit holds every qualifying value: n, and from it the rank
+                unsigned n = 0;
+                for (int g = 0; g < 16; g++) n += sgrp[g];
+                long long kk = (long long)ceil(q.lo * (double)n);
+                kk = kk < 1 ? 1 : (kk > (long long)n ? (long long)n : kk);
+                ssel[2] = n;
+                k = (unsigned)kk;
+            } else {
+                k = ssel[1];
+            }
+            int grp = 15, bin = 15;   // the group of 16 bins, then the bin, in which the running count reaches k
+            bool found = false;
+            for (int g = 0; g < 16; g++) {
+                const unsigned c = sgrp[g];
+                if (!found && k <= c) grp = g, found = true;
+                if (!found) k -= c;
+            }
+            found = false;
+            for (int i = 0; i < 16; i++) {
+                const unsigned c = shist[16 * grp + i];
+                if (!found && k <= c) bin = i, found = true;
+                if (!found) k -= c;
+            }
+            ssel[0] = (unsigned)(16 * grp + bin);
+            ssel[1] = k;
+        }
+        __syncthreads();
+        if (ssel[2] == 0) break;   // (nothing qualifies: every thread reads the same n)
+        prefix |= (unsigned long long)ssel[0] << shift;
+        mask |= 255ull << shift;
+        __syncthreads();   // (ssel and the histogram are read before the next pass writes them)
+    }
+    if (tid == 0) {
+        const unsigned n = ssel[2];
+        counts[j] = (int)n;
+        means[j] = n ? egm_from_bits((prefix >> 63) ? (prefix & ~(1ull << 63)) : ~prefix) : NAN;
     }
 }
 

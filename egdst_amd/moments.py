@@ -3,6 +3,7 @@
     from egdst_amd import moments as mo
     spec = mo.MomentSpec([mo.share('id', k, periods=it) for it in range(nt) for k in range(3)]
                          + [mo.mean('C', periods=(0, 9), where=('id', 2, 2)), mo.cross('M', 'C')], layout=solver.lib.info)
+    spec += [mo.median('M', periods=it) for it in range(nt)] + [mo.quantile('A', 0.9, where=('id', 1, 1))]
     means, counts, obj = solver.simulate_batch_spec(init, spec, target=t, W=W)
     data_means, data_counts = spec.evaluate(data_panel)      # the same definitions, summed in the same order, on the host
 
@@ -10,9 +11,14 @@ Columns are 0-based indices of the simulated panel (egdst_simulate, model.sims) 
 M C A V id ist mu sigma shock u df, then st1.. (nnst states), dc1.. (nnd decisions), eq1.. (neq equations).  `periods` is
 a 0-based model period or an inclusive (first, last) pair; None pools every period.  `where=(col, lo, hi)` keeps the
 (agent, period) pairs with lo <= sims[col] <= hi.
+
+A quantile (kind 3) is an order statistic, not an interpolation: of the n qualifying values the k-th smallest,
+k = ceil(p * n) clamped to [1, n], in the total order of the keys of `quantile_keys` (-0.0 before +0.0); the median of an even
+n is the lower middle value.  The device selects it exactly, so `evaluate` returns the same bits for every block size.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -22,7 +28,7 @@ MOMENT_DTYPE = np.dtype([('kind', '<i4'), ('col', '<i4'), ('col2', '<i4'), ('it_
                          ('cond_col', '<i4'), ('lo', '<f8'), ('hi', '<f8'), ('cond_lo', '<f8'), ('cond_hi', '<f8')])
 
 BASE_COLUMNS = ['M', 'C', 'A', 'V', 'id', 'ist', 'mu', 'sigma', 'shock', 'u', 'df']
-MEAN, CROSS, SHARE = 0, 1, 2
+MEAN, CROSS, SHARE, QUANTILE = 0, 1, 2, 3
 
 
 def columns(nnst, nnd, neq):
@@ -71,6 +77,28 @@ def share(col, lo, hi=None, periods=None, where=None):
     return Moment(SHARE, col, periods=periods, where=where, lo=float(lo), hi=float(lo if hi is None else hi))
 
 
+def quantile(col, p, periods=None, where=None):
+    """quantile p (0 < p < 1) of the present values of sims[col]: the ceil(p n)-th smallest of the n, no interpolation"""
+    return Moment(QUANTILE, col, periods=periods, where=where, lo=float(p))
+
+
+def median(col, periods=None, where=None):
+    """quantile(col, 0.5): the lower middle value of an even number of values"""
+    return quantile(col, 0.5, periods=periods, where=where)
+
+
+def quantile_keys(x):
+    """the uint64 keys whose unsigned order is the order of the quantiles (include/egdst.h): bits u -> ~u if the sign bit is
+    set, else u | 1 << 63"""
+    u = np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    return np.where(u >> np.uint64(63) != 0, ~u, u | np.uint64(1 << 63))
+
+
+def quantile_rank(p, n):
+    """1-based rank of quantile p among n >= 1 values: ceil of the one fp64 product p * n, clamped to [1, n]"""
+    return min(max(int(math.ceil(float(p) * float(n))), 1), int(n))
+
+
 class MomentSpec(list):
     """A list of Moment records, resolved against a model's column layout (`layout`: the library's model info, a Solver, a
     ModelLibrary, a model, or (nnst, nnd, neq)).  pack(nt) gives the egdst_moment array; evaluate(sims) the moments of a host panel."""
@@ -110,8 +138,8 @@ class MomentSpec(list):
         out = np.zeros(len(self), dtype=MOMENT_DTYPE)
         for j, q in enumerate(self):
             what = 'moment %d' % j
-            if not isinstance(q, Moment) or q.kind not in (MEAN, CROSS, SHARE):
-                raise ValueError('MomentSpec: %s is not a mean, cross or share' % what)
+            if not isinstance(q, Moment) or q.kind not in (MEAN, CROSS, SHARE, QUANTILE):
+                raise ValueError('MomentSpec: %s is not a mean, cross, share or quantile' % what)
             col = self._col(q.col, nm, what)
             col2 = self._col(q.col2, nm, what) if q.kind == CROSS else col
             if q.periods is None:
@@ -136,13 +164,16 @@ class MomentSpec(list):
                     raise ValueError('MomentSpec: where of %s has lo > hi' % what)
             if q.kind == SHARE and not q.lo <= q.hi:
                 raise ValueError('MomentSpec: share %s has lo > hi' % what)
+            if q.kind == QUANTILE and not 0.0 < q.lo < 1.0:   # (NaN fails both)
+                raise ValueError('MomentSpec: quantile %s has p = %r outside (0, 1)' % (what, q.lo))
             out[j] = (q.kind, col, col2, f, l_, cc, q.lo, q.hi, clo, chi)
         return out
 
     def evaluate(self, sims, block=256, layout=None):
         """(means [nmom], counts [nmom]) of a host panel sims [nsim, nt, nout] (NaN = missing) with the definitions and the
         summation order of the device (include/egdst.h): per partial t < block the agents i = t (mod block) in ascending i,
-        periods ascending within an agent, then the fixed tree over the partials.  block=256 is the GPU's."""
+        periods ascending within an agent, then the fixed tree over the partials.  block=256 is the GPU's.  A quantile is
+        the key of rank quantile_rank(p, n) among the sorted keys of the qualifying values, whatever the block."""
         sims = np.asarray(sims, dtype=np.float64)
         if sims.ndim != 3:
             raise ValueError('MomentSpec.evaluate: sims must be [nsim, nt, nout]')
@@ -165,6 +196,15 @@ class MomentSpec(list):
             if q['cond_col'] >= 0:
                 c = sims[:, f:l_, q['cond_col']]
                 ok &= (c >= q['cond_lo']) & (c <= q['cond_hi'])
+            if q['kind'] == QUANTILE:
+                n = int(ok.sum())
+                counts[j] = n
+                means[j] = np.nan
+                if n:
+                    key = np.sort(quantile_keys(v[ok]))[quantile_rank(q['lo'], n) - 1]
+                    u = key & np.uint64((1 << 63) - 1) if key >> np.uint64(63) else ~key
+                    means[j] = np.array([u], dtype=np.uint64).view(np.float64)[0]
+                continue
             if q['kind'] == CROSS:
                 w = sims[:, f:l_, q['col2']]
                 ok &= ~np.isnan(w)

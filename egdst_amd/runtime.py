@@ -35,7 +35,7 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_get_checksums', 'egdst_math_eval', 'egdst_get_evals_credited', 'egdst_simulate_batch_moments',
                'egdst_uniform', 'egdst_set_dbgout', 'egdst_get_dbgout', 'egdst_get_walk_stats',
                'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_group_profile',
-               'egdst_simulate_batch_spec']
+               'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys']
 
 
 class EgdstRuntimeError(RuntimeError):
@@ -112,6 +112,9 @@ class ModelLibrary:
         L.egdst_get_profile.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
         L.egdst_get_checksums.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.egdst_math_eval.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.egdst_quantile_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_int)]
+        L.egdst_quantile_lds_keys.argtypes = []
         L.egdst_device_tables.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_void_p)] * 4
         info = EgdstModelInfo()
         L.egdst_get_model_info(C.byref(info))
@@ -142,6 +145,21 @@ class ModelLibrary:
         out = np.zeros_like(x)
         self.check(self.lib.egdst_math_eval({'exp': 0, 'log': 1, 'pow': 2}[fn], x.size, _dp(x), _dp(y), _dp(out)))
         return out
+
+    @property
+    def quantile_lds_keys(self):
+        """candidates up to which k_quantiles selects in LDS (the library's QNT_LDS_KEYS, egdst_quantile_lds_keys)"""
+        return int(self.lib.egdst_quantile_lds_keys())
+
+    def quantile_eval(self, x, p):
+        """(quantiles p of the host array x by the device's selection, the number of non-NaN values): egdst_quantile_eval,
+        the kernel of the kind-3 moments on caller-supplied values."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        p = np.ascontiguousarray(np.atleast_1d(p), dtype=np.float64).reshape(-1)
+        out = np.zeros(p.size)
+        cnt = C.c_int(0)
+        self.check(self.lib.egdst_quantile_eval(x.size, _dp(x), p.size, _dp(p), _dp(out), C.byref(cnt)))
+        return out, cnt.value
 
 
 class Solution:

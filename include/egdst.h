@@ -196,6 +196,13 @@ int egdst_simulate_batch_moments(egdst_handle *h, const double *init, int nsim, 
  *   kind 0  mean of sims[col]
  *   kind 1  mean of sims[col] * sims[col2]                      (both present)
  *   kind 2  share with lo <= sims[col] <= hi among those pairs  (a choice share: col = 4, lo = hi = k)
+ *   kind 3  quantile p of sims[col], p carried in lo with 0 < p < 1 (hi and col2 are ignored): an order statistic, by exact
+ *           selection on the device.  The qualifying values are those of kind 0 and count is n, their number (n = 0: NaN
+ *           mean, count 0).  Rank: t = p * (double)n, one fp64 product; k = (long long)ceil(t), clamped to [1, n].  The k-th
+ *           smallest qualifying value (1-based) is the "mean", its bit pattern untouched: no interpolation, so the median of
+ *           an even n is the lower middle value.  "Smaller" is the total order of the keys u = bits(x),
+ *           key = (u >> 63) ? ~u : u | 1<<63, compared as unsigned 64-bit: -0.0 comes before +0.0, -inf first, +inf last.
+ *           No floating-point arithmetic beyond t, hence no summation order: the value is exact whatever the block size.
  * Columns are 0-based as in egdst_simulate (nout = 11+nnst+nnd+neq); periods are 0-based model periods. */
 typedef struct {
     int kind, col, col2, it_first, it_last, cond_col;
@@ -214,9 +221,10 @@ typedef struct {
  *   A kind-0 moment over one period without condition is exactly the egdst_simulate_batch_moments cell.
  *   r_j = sum over k ascending of W_jk * e_k, skipping W_jk == 0; obj = sum over j ascending of e_j * r_j, skipping the j
  *   whose row of W is all zero (a diagonal W gives the bits of egdst_simulate_batch_moments' objective).
- * EGDST_E_ARG before anything is launched if a kind is not 0..2, a column is outside [0, nout) (cond_col -1: no
- * condition), a period range is empty or outside [0, nt), nmom <= 0, nsim times the periods of a moment exceeds INT_MAX,
- * obj_dev is given without target and W, or no output is given. */
+ * EGDST_E_ARG before anything is launched if a kind is not 0..3, the p (lo) of a kind-3 moment is NaN or outside the open
+ * interval (0, 1), a column is outside [0, nout) (cond_col -1: no condition), a period range is empty or outside [0, nt),
+ * nmom <= 0, nsim times the periods of a moment exceeds INT_MAX, obj_dev is given without target and W, or no output is
+ * given. */
 int egdst_simulate_batch_spec(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
                               long long nrand, unsigned long long seed, int rndtype,
                               const egdst_moment *spec, int nmom,
@@ -282,6 +290,14 @@ int egdst_get_checksums(egdst_handle *h, int draw, unsigned long long *out /* [n
  * fn 3, 4: the interpolation of linter (egdst_lib.c:186-189), f0 (g1 - x) / (g1 - g0) + f1 (x - g0) / (g1 - g0), in the form the grid
  * kernels use (3: one refined reciprocal serves both quotients) and as written (4); x = [x | g0 | g1] (3n values), y = [f0 | f1] (2n). */
 int egdst_math_eval(int fn, int n, const double *x, const double *y, double *out);
+
+/* Quantiles p[0..np) of the host array x[0..n) by the device's selection: x is laid out as column 0 of an [n][1][nout] panel
+ * (the other columns NaN) and k_quantiles runs on np kind-3 records.  NaNs in x do not qualify.  out [np], count [1].
+ * EGDST_E_ARG if n < 1, np < 1 or a p is not inside (0, 1). */
+int egdst_quantile_eval(int n, const double *x, int np, const double *p, double *out, int *count);
+/* Candidates (agents times periods of a kind-3 moment) up to which this library's k_quantiles gathers the keys into LDS
+ * once; a moment with more reads its column from memory in every pass of the selection (build constant QNT_LDS_KEYS). */
+int egdst_quantile_lds_keys(void);
 
 /* Envelope walks of the last solve per draw: out[2*draw] = walks that were cut into segments (one wave each) and merged,
  * out[2*draw+1] = walks whose segment predictions failed the check and were redone by one wave (results are the same
