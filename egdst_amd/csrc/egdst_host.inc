@@ -68,7 +68,7 @@ struct egdst_handle {
     double *sim_init, *sim_rs, *sim_sims, *sim_means;
     int *sim_err, *sim_counts;
     size_t sim_init_bytes, sim_rs_bytes, sim_sims_bytes, sim_means_bytes, sim_err_bytes, sim_counts_bytes;
-    egdst_moment *sim_spec;     // estimation_step: the moment records (egdst_simulate_batch_spec), the target and the weighting
+    egdst_moment_lag *sim_spec; // estimation_step: the moment records (egdst_simulate_batch_spec[_lag]), the target and the weighting
     double *sim_tgt, *sim_W;    // matrix, or its diagonal (egdst_simulate_batch_moments)
     size_t sim_spec_bytes, sim_tgt_bytes, sim_W_bytes;
     size_t klog_bytes;  // kink log (egdst_set_dbgout), allocated apart from the pool
@@ -1398,7 +1398,7 @@ extern "C" int egdst_simulate_moments(egdst_handle *h, int draw, const double *i
     if (!rc) rc = sim_reserve((void **)&h->sim_counts, &h->sim_counts_bytes, sizeof(int) * ncell);
     if (rc) return rc;
     hipLaunchKernelGGL(k_moments, dim3(ncell), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_sims, nsim, nt,
-                       (const egdst_moment *)nullptr, ncell, h->sim_means, h->sim_counts);
+                       (const egdst_moment_lag *)nullptr, ncell, h->sim_means, h->sim_counts);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(means, h->sim_means, sizeof(double) * ncell, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(counts, h->sim_counts, sizeof(int) * ncell, hipMemcpyDeviceToHost, h->stream));
@@ -1416,22 +1416,22 @@ extern "C" double egdst_uniform(unsigned long long seed, unsigned long long k) {
 // k_moments reduces the paths to nmom moments per draw (k_quantiles those that are quantiles, launched only for a spec that has
 // one) and k_moment_objective forms the draw's distance to the target.
 // spec == nullptr: the moments are the nmom = EG_NOUT * nt per-period cells and W [nmom] is the diagonal of the weighting;
-// otherwise spec [nmom] (host) and W [nmom x nmom].  Draws [d0, d0+nd) are simulated together as long as their paths fit
+// otherwise spec [nmom] (host; the device sees the one record type, egdst_moment_lag) and W [nmom x nmom].  Draws [d0, d0+nd) are simulated together as long as their paths fit
 // EG_SIM_SLICE_BYTES, and a slice is reduced on the handle's stream before the next one overwrites the paths
 // (run_simulation waits for its kernel).  Nothing but the objective and, if asked for, the moments is written for the caller.
 static int estimation_step(egdst_handle *h, const double *init, int nsim, const double *randstream_dev, long long nrand,
-                           unsigned long long seed, int rndtype, const egdst_moment *spec, int nmom, const double *target,
+                           unsigned long long seed, int rndtype, const egdst_moment_lag *spec, int nmom, const double *target,
                            const double *W, double *means_dev, int *counts_dev, double *obj_dev)
 {
     const Geom &g = h->b.g;
     const size_t nW = spec ? (size_t)nmom * nmom : (size_t)nmom;
     int rc = sim_reserve((void **)&h->sim_means, &h->sim_means_bytes, sizeof(double) * (size_t)nmom * g.ndraw);
     if (!rc) rc = sim_reserve((void **)&h->sim_counts, &h->sim_counts_bytes, sizeof(int) * (size_t)nmom * g.ndraw);
-    if (!rc && spec) rc = sim_reserve((void **)&h->sim_spec, &h->sim_spec_bytes, sizeof(egdst_moment) * (size_t)nmom);
+    if (!rc && spec) rc = sim_reserve((void **)&h->sim_spec, &h->sim_spec_bytes, sizeof(egdst_moment_lag) * (size_t)nmom);
     if (!rc && obj_dev) rc = sim_reserve((void **)&h->sim_tgt, &h->sim_tgt_bytes, sizeof(double) * (size_t)nmom);
     if (!rc && obj_dev) rc = sim_reserve((void **)&h->sim_W, &h->sim_W_bytes, sizeof(double) * nW);
     if (rc) return rc;
-    if (spec) HIPCHK(hipMemcpyAsync(h->sim_spec, spec, sizeof(egdst_moment) * (size_t)nmom, hipMemcpyHostToDevice, h->stream));
+    if (spec) HIPCHK(hipMemcpyAsync(h->sim_spec, spec, sizeof(egdst_moment_lag) * (size_t)nmom, hipMemcpyHostToDevice, h->stream));
     if (obj_dev) {
         HIPCHK(hipMemcpyAsync(h->sim_tgt, target, sizeof(double) * (size_t)nmom, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->sim_W, W, sizeof(double) * nW, hipMemcpyHostToDevice, h->stream));
@@ -1451,11 +1451,11 @@ static int estimation_step(egdst_handle *h, const double *init, int nsim, const 
         rc = run_simulation(h, d0, nd, 1, init, nsim, nullptr, randstream_dev, nrand, seed, rndtype);
         if (rc) return rc;
         hipLaunchKernelGGL(k_moments, dim3(nmom, nd), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_sims, nsim, g.nt,
-                           spec ? (const egdst_moment *)h->sim_spec : nullptr, nmom, h->sim_means + (size_t)d0 * nmom,
+                           spec ? (const egdst_moment_lag *)h->sim_spec : nullptr, nmom, h->sim_means + (size_t)d0 * nmom,
                            h->sim_counts + (size_t)d0 * nmom);
         if (q_last >= q_first)   // the quantile records, which k_moments leaves alone
             hipLaunchKernelGGL(k_quantiles, dim3(q_last - q_first + 1, nd), dim3(QNT_BS), 0, h->stream, (const double *)h->sim_sims,
-                               nsim, g.nt, (const egdst_moment *)h->sim_spec, q_first, nmom, h->sim_means + (size_t)d0 * nmom,
+                               nsim, g.nt, (const egdst_moment_lag *)h->sim_spec, q_first, nmom, h->sim_means + (size_t)d0 * nmom,
                                h->sim_counts + (size_t)d0 * nmom);
     }
     if (obj_dev)
@@ -1483,19 +1483,25 @@ extern "C" int egdst_simulate_batch_moments(egdst_handle *h, const double *init,
                            means_dev, counts_dev, obj_dev);
 }
 
-// The step with user-defined moments (egdst_moment) and a full weighting matrix: the objective is e' W e.  Every argument
-// is checked before anything is enqueued.
+// The step with user-defined moments and a full weighting matrix: the objective is e' W e.  Every argument is checked before
+// anything is enqueued.  The device sees one record type, egdst_moment_lag; egdst_simulate_batch_spec promotes its
+// egdst_moment records with zero lags and `who` names the door in the messages.
 static_assert(sizeof(egdst_moment) == 56, "egdst_moment is 6 ints and 4 doubles (the Python dtype mirrors it)");
-extern "C" int egdst_simulate_batch_spec(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
-                                         long long nrand, unsigned long long seed, int rndtype, const egdst_moment *spec,
-                                         int nmom, const double *target, const double *W, double *means_dev, int *counts_dev,
-                                         double *obj_dev)
+static_assert(sizeof(egdst_moment_lag) == 64 && offsetof(egdst_moment_lag, lag2) == 56 && offsetof(egdst_moment_lag, cond_lag) == 60,
+              "egdst_moment_lag is egdst_moment and 2 ints (the Python dtype mirrors it)");
+// Do the periods [it_first, it_last] shifted by -lag stay inside [0, nt)?  (64-bit: no int lag overflows)
+static bool lag_inside(int it_first, int it_last, int lag, int nt)
 {
-    if (!h || !spec || nmom <= 0 || (obj_dev && (!target || !W)) || (!obj_dev && !means_dev && !counts_dev))
-        return set_err(EGDST_E_ARG, "egdst_simulate_batch_spec: bad arguments");
+    return (long long)it_first - lag >= 0 && (long long)it_last - lag < nt;
+}
+
+static int checked_estimation_step(const char *who, egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
+                                   long long nrand, unsigned long long seed, int rndtype, const egdst_moment_lag *spec, int nmom,
+                                   const double *target, const double *W, double *means_dev, int *counts_dev, double *obj_dev)
+{
     const int nout = EG_NOUT, nt = h->b.g.nt;
     for (int j = 0; j < nmom; j++) {
-        const egdst_moment &q = spec[j];
+        const egdst_moment_lag &q = spec[j];
         const char *bad = nullptr;
         if (q.kind < 0 || q.kind > 3) bad = "kind is not 0, 1, 2 or 3";
         else if (q.kind == 3 && !(q.lo > 0.0 && q.lo < 1.0)) bad = "the p of a quantile (lo) is not inside (0, 1)";   // (NaN fails both)
@@ -1504,10 +1510,42 @@ extern "C" int egdst_simulate_batch_spec(egdst_handle *h, const double *init, in
         else if (q.cond_col < -1 || q.cond_col >= nout) bad = "cond_col is outside the simulated columns";
         else if (q.it_first < 0 || q.it_last < q.it_first || q.it_last >= nt) bad = "the period range is empty or outside the model's";
         else if (nsim > 0 && (long long)nsim * (q.it_last - q.it_first + 1) > 2147483647LL) bad = "nsim times its periods overflows a count";
-        if (bad) return set_err(EGDST_E_ARG, "egdst_simulate_batch_spec: moment %d: %s", j, bad);
+        else if (q.lag2 != 0 && q.kind != 1) bad = "lag2 is set on a kind other than 1";
+        else if (q.cond_lag != 0 && q.cond_col == -1) bad = "cond_lag is set without a condition";
+        else if (!lag_inside(q.it_first, q.it_last, q.lag2, nt)) bad = "the period range shifted by lag2 leaves the model's periods";
+        else if (!lag_inside(q.it_first, q.it_last, q.cond_lag, nt)) bad = "the period range shifted by cond_lag leaves the model's periods";
+        if (bad) return set_err(EGDST_E_ARG, "%s: moment %d: %s", who, j, bad);
     }
     return estimation_step(h, init, nsim, randstream_dev, nrand, seed, rndtype, spec, nmom, target, W, means_dev, counts_dev,
                            obj_dev);
+}
+
+extern "C" int egdst_simulate_batch_spec(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
+                                         long long nrand, unsigned long long seed, int rndtype, const egdst_moment *spec,
+                                         int nmom, const double *target, const double *W, double *means_dev, int *counts_dev,
+                                         double *obj_dev)
+{
+    if (!h || !spec || nmom <= 0 || (obj_dev && (!target || !W)) || (!obj_dev && !means_dev && !counts_dev))
+        return set_err(EGDST_E_ARG, "egdst_simulate_batch_spec: bad arguments");
+    egdst_moment_lag *rec = (egdst_moment_lag *)calloc((size_t)nmom, sizeof(egdst_moment_lag));   // (zero lags)
+    if (!rec) return set_err(EGDST_E_HIP, "egdst_simulate_batch_spec: out of host memory");
+    for (int j = 0; j < nmom; j++) memcpy(&rec[j], &spec[j], sizeof(egdst_moment));
+    const int rc = checked_estimation_step("egdst_simulate_batch_spec", h, init, nsim, randstream_dev, nrand, seed, rndtype, rec, nmom,
+                                           target, W, means_dev, counts_dev, obj_dev);
+    if (rc) (void)hipStreamSynchronize(h->stream);   // (a failed step may leave the upload of rec enqueued)
+    free(rec);
+    return rc;
+}
+
+extern "C" int egdst_simulate_batch_spec_lag(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
+                                             long long nrand, unsigned long long seed, int rndtype, const egdst_moment_lag *spec,
+                                             int nmom, const double *target, const double *W, double *means_dev, int *counts_dev,
+                                             double *obj_dev)
+{
+    if (!h || !spec || nmom <= 0 || (obj_dev && (!target || !W)) || (!obj_dev && !means_dev && !counts_dev))
+        return set_err(EGDST_E_ARG, "egdst_simulate_batch_spec_lag: bad arguments");
+    return checked_estimation_step("egdst_simulate_batch_spec_lag", h, init, nsim, randstream_dev, nrand, seed, rndtype, spec, nmom,
+                                   target, W, means_dev, counts_dev, obj_dev);
 }
 
 // egdst_call.c:17-164.  The index checks of the gateway are done here, in row order, because an out-of-range index
@@ -1746,10 +1784,10 @@ extern "C" int egdst_quantile_eval(int n, const double *x, int np, const double 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_err(EGDST_E_NOGPU, "%s", egdst_strerror(EGDST_E_NOGPU));
     const size_t npanel = (size_t)n * EG_NOUT;
     double *panel = (double *)malloc(sizeof(double) * npanel);
-    egdst_moment *rec = (egdst_moment *)calloc((size_t)np, sizeof(egdst_moment));
+    egdst_moment_lag *rec = (egdst_moment_lag *)calloc((size_t)np, sizeof(egdst_moment_lag));
     int *cnt = (int *)malloc(sizeof(int) * (size_t)np);
     double *d_panel = nullptr, *d_means = nullptr;
-    egdst_moment *d_rec = nullptr;
+    egdst_moment_lag *d_rec = nullptr;
     int *d_cnt = nullptr;
     if (!panel || !rec || !cnt) {
         free(panel), free(rec), free(cnt);
@@ -1759,13 +1797,13 @@ extern "C" int egdst_quantile_eval(int n, const double *x, int np, const double 
     for (int i = 0; i < n; i++) panel[(size_t)i * EG_NOUT] = x[i];
     for (int i = 0; i < np; i++) rec[i].kind = 3, rec[i].cond_col = -1, rec[i].lo = p[i];
     hipError_t e = hipMalloc(&d_panel, sizeof(double) * npanel);
-    if (e == hipSuccess) e = hipMalloc(&d_rec, sizeof(egdst_moment) * (size_t)np);
+    if (e == hipSuccess) e = hipMalloc(&d_rec, sizeof(egdst_moment_lag) * (size_t)np);
     if (e == hipSuccess) e = hipMalloc(&d_means, sizeof(double) * (size_t)np);
     if (e == hipSuccess) e = hipMalloc(&d_cnt, sizeof(int) * (size_t)np);
     if (e == hipSuccess) e = hipMemcpy(d_panel, panel, sizeof(double) * npanel, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rec, rec, sizeof(egdst_moment) * (size_t)np, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rec, rec, sizeof(egdst_moment_lag) * (size_t)np, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_quantiles, dim3(np), dim3(QNT_BS), 0, 0, (const double *)d_panel, n, 1, (const egdst_moment *)d_rec, 0, np,
+        hipLaunchKernelGGL(k_quantiles, dim3(np), dim3(QNT_BS), 0, 0, (const double *)d_panel, n, 1, (const egdst_moment_lag *)d_rec, 0, np,
                            d_means, d_cnt);
         e = hipGetLastError();
     }

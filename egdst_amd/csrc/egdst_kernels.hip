@@ -4802,26 +4802,47 @@ __global__ void __launch_bounds__(GRID_BS) k_call(const Batch *bp_, CallArgs a)
 #define MOM_BS 256
 #endif
 // Moment j of the fixed set, the mean of one (column, period) cell of the paths: j = col + nout * it.
-static __device__ __forceinline__ egdst_moment eg_cell_moment(int j)
+static __device__ __forceinline__ egdst_moment_lag eg_cell_moment(int j)
 {
-    egdst_moment q = {};
+    egdst_moment_lag q = {};
     q.col = j % EG_NOUT;
     q.it_first = q.it_last = j / EG_NOUT;
     q.cond_col = -1;
     return q;
 }
 
-// One moment (egdst_moment, include/egdst.h) of one draw's simulated paths: spec[j], or with spec == nullptr cell j of the
+// Does the pair (agent, it) qualify for record q (egdst_moment_lag, include/egdst.h), and with which value?  o is the agent's
+// row of period it; the condition is read cond_lag rows and the second factor of a cross lag2 rows before it (the host
+// checked that those periods exist; with zero lags all three reads are in the row o).  *x: the value v, for kind 1 the
+// product v * w.  The moment kernel and the quantiles' candidates share this routine, so the two-period reads exist once.
+static __device__ __forceinline__ bool eg_moment_term(const double *o, const egdst_moment_lag &q, double *x)
+{
+    const double v = o[q.col];
+    if (!(v == v)) return false;
+    if (q.cond_col >= 0) {
+        const double c = (o - (ptrdiff_t)q.cond_lag * EG_NOUT)[q.cond_col];
+        if (!(c >= q.cond_lo && c <= q.cond_hi)) return false;   // (NaN fails both)
+    }
+    *x = v;
+    if (q.kind == 1) {
+        const double w = (o - (ptrdiff_t)q.lag2 * EG_NOUT)[q.col2];
+        if (!(w == w)) return false;
+        *x = v * w;
+    }
+    return true;
+}
+
+// One moment (egdst_moment_lag, include/egdst.h) of one draw's simulated paths: spec[j], or with spec == nullptr cell j of the
 // fixed set.  The agents without a value (NaN: died, or started outside the admissible range) do not count.  One workgroup
 // per (moment, draw of the launch); each thread adds the qualifying values of its agents in index order, within an agent in
 // period order, then a fixed tree over the threads: the result does not depend on scheduling.
-__global__ void __launch_bounds__(MOM_BS) k_moments(const double *sims, int nsim, int nt, const egdst_moment *spec, int nmom,
+__global__ void __launch_bounds__(MOM_BS) k_moments(const double *sims, int nsim, int nt, const egdst_moment_lag *spec, int nmom,
                                                     double *means, int *counts)
 {
     __shared__ double ssum[MOM_BS];
     __shared__ int scnt[MOM_BS];
     const int j = blockIdx.x, tid = threadIdx.x;
-    const egdst_moment q = spec ? spec[j] : eg_cell_moment(j);
+    const egdst_moment_lag q = spec ? spec[j] : eg_cell_moment(j);
     if (q.kind == 3) return;   // (a quantile: k_quantiles writes it; the whole workgroup leaves, ahead of every barrier)
     const size_t per_agent = (size_t)EG_NOUT * nt;
     sims += (size_t)blockIdx.y * per_agent * nsim;   // (one set of paths, means and counts per draw of the launch)
@@ -4832,21 +4853,9 @@ __global__ void __launch_bounds__(MOM_BS) k_moments(const double *sims, int nsim
     for (int i = tid; i < nsim; i += MOM_BS) {
         const double *p = sims + (size_t)i * per_agent;
         for (int it = q.it_first; it <= q.it_last; it++) {
-            const double *o = p + (size_t)it * EG_NOUT;
-            const double v = o[q.col];
-            if (!(v == v)) continue;
-            if (q.cond_col >= 0) {
-                const double c = o[q.cond_col];
-                if (!(c >= q.cond_lo && c <= q.cond_hi)) continue;   // (NaN fails both)
-            }
-            double x = v;
-            if (q.kind == 1) {
-                const double w = o[q.col2];
-                if (!(w == w)) continue;
-                x = v * w;
-            } else if (q.kind == 2) {
-                x = (v >= q.lo && v <= q.hi) ? 1.0 : 0.0;
-            }
+            double x;
+            if (!eg_moment_term(p + (size_t)it * EG_NOUT, q, &x)) continue;
+            if (q.kind == 2) x = (x >= q.lo && x <= q.hi) ? 1.0 : 0.0;
             acc += x, cnt++;
         }
     }
@@ -4883,21 +4892,17 @@ static __device__ __forceinline__ unsigned long long qnt_key(unsigned long long 
     return (u >> 63) ? ~u : (u | (1ull << 63));
 }
 
-// Key of candidate c of record q: agent c / np, period it_first + c % np (np periods); 0 if the pair does not qualify.
-static __device__ __forceinline__ unsigned long long qnt_candidate(const double *sims, size_t per_agent, const egdst_moment &q,
+// Key of candidate c of record q: agent c / np, period it_first + c % np (np periods); 0 if the pair does not qualify
+// (eg_moment_term, which hands a kind-3 record its value untouched).
+static __device__ __forceinline__ unsigned long long qnt_candidate(const double *sims, size_t per_agent, const egdst_moment_lag &q,
                                                                    int np, int c)
 {
-    const double *o = sims + (size_t)(c / np) * per_agent + (size_t)(q.it_first + c % np) * EG_NOUT;
-    const unsigned long long u = egm_bits(o[q.col]);
-    if ((u & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) return 0;   // NaN
-    if (q.cond_col >= 0) {
-        const double cv = o[q.cond_col];
-        if (!(cv >= q.cond_lo && cv <= q.cond_hi)) return 0;   // (NaN fails both)
-    }
-    return qnt_key(u);
+    double x;
+    if (!eg_moment_term(sims + (size_t)(c / np) * per_agent + (size_t)(q.it_first + c % np) * EG_NOUT, q, &x)) return 0;
+    return qnt_key(egm_bits(x));
 }
 
-// Quantile moments (kind 3 of egdst_moment, include/egdst.h) of one draw's simulated paths by exact selection: one workgroup
+// Quantile moments (kind 3 of egdst_moment_lag, include/egdst.h) of one draw's simulated paths by exact selection: one workgroup
 // per (record j0 + blockIdx.x, draw of the launch); records of another kind leave at once.  Most-significant-digit radix
 // select on the 64-bit keys: pass d counts, in a 256-bin histogram, byte 7 - d of the keys that agree with the digits
 // selected so far, the bin that holds rank k becomes the next digit and k the rank inside it; after eight passes the digits
@@ -4905,7 +4910,7 @@ static __device__ __forceinline__ unsigned long long qnt_candidate(const double 
 // candidates (nsim times its periods) gathers its keys into LDS once -- a column read is strided by EG_NOUT doubles -- the
 // others read the column in every pass.  Every loop with a barrier has workgroup-uniform bounds; what one thread decides
 // (n, the bin, the new k) goes through LDS and a barrier.
-__global__ void __launch_bounds__(QNT_BS) k_quantiles(const double *sims, int nsim, int nt, const egdst_moment *spec, int j0,
+__global__ void __launch_bounds__(QNT_BS) k_quantiles(const double *sims, int nsim, int nt, const egdst_moment_lag *spec, int j0,
                                                       int nmom, double *means, int *counts)
 {
     __shared__ unsigned long long skey[QNT_LDS_KEYS];
@@ -4913,7 +4918,7 @@ __global__ void __launch_bounds__(QNT_BS) k_quantiles(const double *sims, int ns
     __shared__ unsigned sgrp[16];   // sums of 16 bins each
     __shared__ unsigned ssel[3];    // selected bin, rank inside it, n
     const int j = j0 + blockIdx.x, tid = threadIdx.x;
-    const egdst_moment q = spec[j];
+    const egdst_moment_lag q = spec[j];
     if (q.kind != 3) return;   // (the whole workgroup, ahead of every barrier)
     const size_t per_agent = (size_t)EG_NOUT * nt;
     sims += (size_t)blockIdx.y * per_agent * nsim;

@@ -12,6 +12,19 @@ M C A V id ist mu sigma shock u df, then st1.. (nnst states), dc1.. (nnd decisio
 a 0-based model period or an inclusive (first, last) pair; None pools every period.  `where=(col, lo, hi)` keeps the
 (agent, period) pairs with lo <= sims[col] <= hi.
 
+Moments across two periods (egdst_moment_lag, egdst_simulate_batch_spec_lag): a lag counts periods back (> 0) or ahead (< 0).
+`where=(col, lo, hi, lag)` reads the condition in period it - lag, `cross(col, col2, lag=k)` multiplies sims[col] in period it
+by sims[col2] in period it - k, and `transition(col, frm, to)` is the share moving to `to` among those who were at `frm` a
+period earlier:
+
+    spec = mo.MomentSpec([mo.transition('id', 1, 0, periods=it) for it in range(1, nt)]       # a hazard by age
+                         + [mo.cross('C', 'C', lag=1), mo.mean('C', where=('id', 0, 0, -1))], layout=solver.lib.info)
+
+A pair counts only if every value it reads is present in its own period (NaN never qualifies), so an agent that is dead or
+not yet valued in the other period drops out.  With a lag, `periods=None` pools every period for which the other periods
+exist, first = max(0, lags in use) to last = nt - 1 + min(0, lags in use); an explicit range that reaches outside raises
+ValueError: nothing is clipped.  A spec with a lag packs with pack_lag (MOMENT_LAG_DTYPE, 64 bytes); pack() refuses it.
+
 A quantile (kind 3) is an order statistic, not an interpolation: of the n qualifying values the k-th smallest,
 k = ceil(p * n) clamped to [1, n], in the total order of the keys of `quantile_keys` (-0.0 before +0.0); the median of an even
 n is the lower middle value.  The device selects it exactly, so `evaluate` returns the same bits for every block size.
@@ -26,6 +39,9 @@ import numpy as np
 # egdst_moment: 6 ints, then 4 doubles (56 bytes, no padding)
 MOMENT_DTYPE = np.dtype([('kind', '<i4'), ('col', '<i4'), ('col2', '<i4'), ('it_first', '<i4'), ('it_last', '<i4'),
                          ('cond_col', '<i4'), ('lo', '<f8'), ('hi', '<f8'), ('cond_lo', '<f8'), ('cond_hi', '<f8')])
+
+# egdst_moment_lag: the fields of egdst_moment, then the two lags (64 bytes, no padding)
+MOMENT_LAG_DTYPE = np.dtype(MOMENT_DTYPE.descr + [('lag2', '<i4'), ('cond_lag', '<i4')])
 
 BASE_COLUMNS = ['M', 'C', 'A', 'V', 'id', 'ist', 'mu', 'sigma', 'shock', 'u', 'df']
 MEAN, CROSS, SHARE, QUANTILE = 0, 1, 2, 3
@@ -60,6 +76,7 @@ class Moment:
     where: object = None
     lo: float = 0.0
     hi: float = 0.0
+    lag: int = 0   # (of col2, kind 1 only; a condition's lag is the fourth entry of `where`)
 
 
 def mean(col, periods=None, where=None):
@@ -67,14 +84,21 @@ def mean(col, periods=None, where=None):
     return Moment(MEAN, col, periods=periods, where=where)
 
 
-def cross(col, col2, periods=None, where=None):
-    """mean of sims[col] * sims[col2] over the pairs where both are present (E[x^2] with col2 = col)"""
-    return Moment(CROSS, col, col2, periods=periods, where=where)
+def cross(col, col2, periods=None, where=None, lag=0):
+    """mean of sims[col] * sims[col2] over the pairs where both are present (E[x^2] with col2 = col); col2 is read `lag`
+    periods before col (after it with lag < 0): cross('C', 'C', lag=1) is E[C_t * C_t-1]"""
+    return Moment(CROSS, col, col2, periods=periods, where=where, lag=lag)
 
 
 def share(col, lo, hi=None, periods=None, where=None):
     """share of the present values of sims[col] in [lo, hi] (hi = lo when not given): share('id', k) is choice k's share"""
     return Moment(SHARE, col, periods=periods, where=where, lo=float(lo), hi=float(lo if hi is None else hi))
+
+
+def transition(col, frm, to, periods=None, lag=1):
+    """share of the present values of sims[col] equal to `to` among the pairs whose sims[col] was `frm` `lag` periods before:
+    share(col, to, where=(col, frm, frm, lag)).  transition('id', 0, 1, periods=it) is the hazard of choice 1 in period it."""
+    return share(col, to, periods=periods, where=(col, frm, frm, lag))
 
 
 def quantile(col, p, periods=None, where=None):
@@ -101,7 +125,8 @@ def quantile_rank(p, n):
 
 class MomentSpec(list):
     """A list of Moment records, resolved against a model's column layout (`layout`: the library's model info, a Solver, a
-    ModelLibrary, a model, or (nnst, nnd, neq)).  pack(nt) gives the egdst_moment array; evaluate(sims) the moments of a host panel."""
+    ModelLibrary, a model, or (nnst, nnd, neq)).  pack(nt) gives the egdst_moment array, pack_lag(nt) the egdst_moment_lag array (a
+    spec with a lag has only that one); evaluate(sims) the moments of a host panel."""
 
     def __init__(self, items=(), layout=None):
         super().__init__(items)
@@ -129,21 +154,61 @@ class MomentSpec(list):
             raise ValueError('MomentSpec: column %d of %s is outside [0, %s)' % (c, what, len(names) if names else 'nout'))
         return int(c)
 
+    @staticmethod
+    def _lag(x, what):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            raise ValueError('MomentSpec: lag %r of %s is not an integer number of periods' % (x, what))
+        return int(x)
+
+    @property
+    def lagged(self):
+        """does a moment read a second period (a non-zero lag on col2 or on the condition)?"""
+        return any(isinstance(q, Moment) and (q.lag != 0 or q.where is not None and len(q.where) == 4 and q.where[3] != 0)
+                   for q in self)
+
     def pack(self, nt, layout=None):
-        """[nmom] array of MOMENT_DTYPE; raises ValueError on a bad name, kind, column or period range"""
+        """[nmom] array of MOMENT_DTYPE; raises ValueError on a bad name, kind, column or period range, and on a spec with a
+        lag: that one packs with pack_lag"""
+        if self.lagged:
+            raise ValueError('MomentSpec: a moment has a lag, which egdst_moment cannot carry: use pack_lag')
+        rec = self.pack_lag(nt, layout)
+        out = np.zeros(len(rec), dtype=MOMENT_DTYPE)
+        for f in MOMENT_DTYPE.names:
+            out[f] = rec[f]
+        return out
+
+    def pack_lag(self, nt, layout=None):
+        """[nmom] array of MOMENT_LAG_DTYPE, with or without lags; raises ValueError on a bad name, kind, column, lag or
+        period range: on everything the library refuses"""
         if len(self) == 0:
             raise ValueError('MomentSpec: no moments')
         lay = _layout(layout) or self.layout
         nm = None if lay is None else columns(*lay)
-        out = np.zeros(len(self), dtype=MOMENT_DTYPE)
+        out = np.zeros(len(self), dtype=MOMENT_LAG_DTYPE)
         for j, q in enumerate(self):
             what = 'moment %d' % j
             if not isinstance(q, Moment) or q.kind not in (MEAN, CROSS, SHARE, QUANTILE):
                 raise ValueError('MomentSpec: %s is not a mean, cross, share or quantile' % what)
             col = self._col(q.col, nm, what)
             col2 = self._col(q.col2, nm, what) if q.kind == CROSS else col
-            if q.periods is None:
-                f, l_ = 0, nt - 1
+            lag2 = self._lag(q.lag, what)
+            if lag2 != 0 and q.kind != CROSS:
+                raise ValueError('MomentSpec: %s has a lag but is not a cross (a condition\'s lag goes into where)' % what)
+            cc, clo, chi, clag = -1, 0.0, 0.0, 0
+            if q.where is not None:
+                if len(q.where) not in (3, 4):
+                    raise ValueError('MomentSpec: where of %s is not (col, lo, hi) or (col, lo, hi, lag)' % what)
+                cc = self._col(q.where[0], nm, what)
+                clo, chi = float(q.where[1]), float(q.where[2])
+                if not clo <= chi:
+                    raise ValueError('MomentSpec: where of %s has lo > hi' % what)
+                if len(q.where) == 4:
+                    clag = self._lag(q.where[3], what)
+            lags = [lag2, clag]   # (0 where not in use: a lag of 0 moves neither end)
+            if q.periods is None:   # every period for which the other periods exist
+                f, l_ = max(0, *lags), nt - 1 + min(0, *lags)
+                if f > l_:
+                    raise ValueError('MomentSpec: with lags (%d, %d) %s has no period inside [0, %d)' % (lag2, clag, what, nt))
             elif isinstance(q.periods, (int, np.integer)) and not isinstance(q.periods, bool):
                 f = l_ = int(q.periods)
             else:
@@ -154,26 +219,23 @@ class MomentSpec(list):
                                      % (q.periods, what)) from None
             if not 0 <= f <= l_ < nt:
                 raise ValueError('MomentSpec: periods (%d, %d) of %s are empty or outside [0, %d)' % (f, l_, what, nt))
-            cc, clo, chi = -1, 0.0, 0.0
-            if q.where is not None:
-                if len(q.where) != 3:
-                    raise ValueError('MomentSpec: where of %s is not (col, lo, hi)' % what)
-                cc = self._col(q.where[0], nm, what)
-                clo, chi = float(q.where[1]), float(q.where[2])
-                if not clo <= chi:
-                    raise ValueError('MomentSpec: where of %s has lo > hi' % what)
+            for lag in lags:
+                if f - lag < 0 or l_ - lag >= nt:
+                    raise ValueError('MomentSpec: periods (%d, %d) of %s, read %d periods %s, leave [0, %d)'
+                                     % (f, l_, what, abs(lag), 'back' if lag > 0 else 'ahead', nt))
             if q.kind == SHARE and not q.lo <= q.hi:
                 raise ValueError('MomentSpec: share %s has lo > hi' % what)
             if q.kind == QUANTILE and not 0.0 < q.lo < 1.0:   # (NaN fails both)
                 raise ValueError('MomentSpec: quantile %s has p = %r outside (0, 1)' % (what, q.lo))
-            out[j] = (q.kind, col, col2, f, l_, cc, q.lo, q.hi, clo, chi)
+            out[j] = (q.kind, col, col2, f, l_, cc, q.lo, q.hi, clo, chi, lag2, clag)
         return out
 
     def evaluate(self, sims, block=256, layout=None):
         """(means [nmom], counts [nmom]) of a host panel sims [nsim, nt, nout] (NaN = missing) with the definitions and the
         summation order of the device (include/egdst.h): per partial t < block the agents i = t (mod block) in ascending i,
         periods ascending within an agent, then the fixed tree over the partials.  block=256 is the GPU's.  A quantile is
-        the key of rank quantile_rank(p, n) among the sorted keys of the qualifying values, whatever the block."""
+        the key of rank quantile_rank(p, n) among the sorted keys of the qualifying values, whatever the block.  A lagged
+        condition or second factor is read in period it - lag and must be present there."""
         sims = np.asarray(sims, dtype=np.float64)
         if sims.ndim != 3:
             raise ValueError('MomentSpec.evaluate: sims must be [nsim, nt, nout]')
@@ -183,7 +245,7 @@ class MomentSpec(list):
         lay = _layout(layout) or self.layout
         if lay is not None and 11 + sum(lay) != nout:
             raise ValueError('MomentSpec.evaluate: the panel has %d columns, the layout %d' % (nout, 11 + sum(lay)))
-        rec = self.pack(nt, layout)
+        rec = self.pack_lag(nt, layout)
         if (rec['col'].max(initial=0) >= nout or rec['col2'].max(initial=0) >= nout or rec['cond_col'].max(initial=-1) >= nout):
             raise ValueError('MomentSpec.evaluate: a column is outside the panel\'s %d columns' % nout)
         nb = -(-nsim // block)
@@ -194,8 +256,9 @@ class MomentSpec(list):
             v = sims[:, f:l_, q['col']]
             ok = ~np.isnan(v)
             if q['cond_col'] >= 0:
-                c = sims[:, f:l_, q['cond_col']]
-                ok &= (c >= q['cond_lo']) & (c <= q['cond_hi'])
+                c = sims[:, f - int(q['cond_lag']):l_ - int(q['cond_lag']), q['cond_col']]   # (pack_lag: inside the panel)
+                with np.errstate(invalid='ignore'):
+                    ok &= (c >= q['cond_lo']) & (c <= q['cond_hi'])
             if q['kind'] == QUANTILE:
                 n = int(ok.sum())
                 counts[j] = n
@@ -206,11 +269,13 @@ class MomentSpec(list):
                     means[j] = np.array([u], dtype=np.uint64).view(np.float64)[0]
                 continue
             if q['kind'] == CROSS:
-                w = sims[:, f:l_, q['col2']]
+                w = sims[:, f - int(q['lag2']):l_ - int(q['lag2']), q['col2']]
                 ok &= ~np.isnan(w)
-                x = v * w
+                with np.errstate(invalid='ignore'):
+                    x = v * w
             elif q['kind'] == SHARE:
-                x = ((v >= q['lo']) & (v <= q['hi'])).astype(np.float64)
+                with np.errstate(invalid='ignore'):
+                    x = ((v >= q['lo']) & (v <= q['hi'])).astype(np.float64)
             else:
                 x = v
             x = np.where(ok, x, 0.0)   # (adding +0.0 leaves a partial unchanged: it starts at +0.0 and never becomes -0.0)

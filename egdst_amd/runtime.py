@@ -35,7 +35,7 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_get_checksums', 'egdst_math_eval', 'egdst_get_evals_credited', 'egdst_simulate_batch_moments',
                'egdst_uniform', 'egdst_set_dbgout', 'egdst_get_dbgout', 'egdst_get_walk_stats',
                'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_group_profile',
-               'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys']
+               'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys', 'egdst_simulate_batch_spec_lag']
 
 
 class EgdstRuntimeError(RuntimeError):
@@ -89,6 +89,7 @@ class ModelLibrary:
         L.egdst_simulate_batch_spec.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_longlong, C.c_ulonglong,
                                                 C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        L.egdst_simulate_batch_spec_lag.argtypes = L.egdst_simulate_batch_spec.argtypes
         L.egdst_uniform.restype = C.c_double
         L.egdst_uniform.argtypes = [C.c_ulonglong, C.c_ulonglong]
         L.egdst_set_dbgout.argtypes = [C.c_void_p, C.c_int]
@@ -553,11 +554,17 @@ class Solver:
         """egdst_simulate_batch_spec: the estimation step of simulate_batch_moments with user-defined moments -- spec is a
         moments.MomentSpec (names resolved with this library's columns) or an array of moments.MOMENT_DTYPE -- and a full
         weighting matrix W ([nmom, nmom], or a vector: its diagonal).  The objective is computed when target and W are given.
+        A MomentSpec with a lag (spec.lagged) or an array of moments.MOMENT_LAG_DTYPE goes to egdst_simulate_batch_spec_lag.
         The *_dev arguments are device pointers (ints); with none given, returns (means [ndraw, nmom], counts [ndraw, nmom],
         objective [ndraw] or None) through torch tensors allocated here."""
         from . import moments
-        if isinstance(spec, moments.MomentSpec):
+        entry = self.lib.lib.egdst_simulate_batch_spec
+        if isinstance(spec, moments.MomentSpec) and spec.lagged:
+            rec, entry = spec.pack_lag(self.nt, layout=self.lib.info), self.lib.lib.egdst_simulate_batch_spec_lag
+        elif isinstance(spec, moments.MomentSpec):
             rec = spec.pack(self.nt, layout=self.lib.info)
+        elif getattr(spec, 'dtype', None) == moments.MOMENT_LAG_DTYPE:
+            rec, entry = np.ascontiguousarray(spec).reshape(-1), self.lib.lib.egdst_simulate_batch_spec_lag
         else:
             rec = np.ascontiguousarray(spec, dtype=moments.MOMENT_DTYPE).reshape(-1)
         nmom = len(rec)
@@ -572,7 +579,7 @@ class Solver:
                 w = moments.weight_matrix(W, nmom)
             except ValueError as e:
                 raise EgdstRuntimeError(1, 'simulate_batch_spec: %s' % e) from None
-        return self._estimation_step(self.lib.lib.egdst_simulate_batch_spec, init, seed, rndtype, randstream_dev, nrand,
+        return self._estimation_step(entry, init, seed, rndtype, randstream_dev, nrand,
                                      (nmom,), (rec.ctypes.data_as(C.c_void_p), nmom), t, w, means_dev, counts_dev, obj_dev)
 
     def call(self, sw, args, draw=0):

@@ -231,6 +231,33 @@ int egdst_simulate_batch_spec(egdst_handle *h, const double *init, int nsim, con
                               const double *target /* [nmom] */, const double *W /* [nmom x nmom] row-major */,
                               double *means_dev /* [ndraw][nmom] */, int *counts_dev /* [ndraw][nmom] */,
                               double *obj_dev /* [ndraw] */);
+/* A moment across two periods: the 56 bytes of egdst_moment with the same meaning, then two lags in periods, back (> 0) or
+ * ahead (< 0).  Pairs (agent, it) run over it_first <= it <= it_last, and the checks come in this order:
+ *   1. v = sims[col][it] must be present;
+ *   2. if cond_col >= 0, c = sims[cond_col][it - cond_lag] must satisfy cond_lo <= c <= cond_hi (NaN never qualifies: an
+ *      agent that is dead or not yet valued in that other period drops out);
+ *   3. kind 1 takes w = sims[col2][it - lag2], which must be present, and x = v * w;
+ *   4. kinds 0, 2 and 3 use v as in egdst_moment.
+ * A retirement hazard is kind 2 on the choice column with cond_col the same column, cond_lo = cond_hi = the origin and
+ * cond_lag = 1; persistence E[x_t x_t-1] is kind 1 with lag2 = 1; "those about to retire" is a condition with cond_lag = -1. */
+typedef struct {
+    int kind, col, col2, it_first, it_last, cond_col;
+    double lo, hi, cond_lo, cond_hi;
+    int lag2, cond_lag;
+} egdst_moment_lag;   /* 64 bytes, no padding */
+
+/* egdst_simulate_batch_spec, argument for argument, on egdst_moment_lag records.  Count, the NaN mean with count 0, the
+ * summation order, the quantile's rank and key order, failed draws, slicing and the objective are those of
+ * egdst_simulate_batch_spec; a record with both lags zero gives the bits of that call on its first 56 bytes.
+ * EGDST_E_ARG before anything is launched, with the moment's index in egdst_last_error: everything egdst_simulate_batch_spec
+ * refuses; lag2 != 0 on a kind other than 1; cond_lag != 0 with cond_col == -1; a lag in use for which it_first - lag < 0 or
+ * it_last - lag >= nt (any int lag; the period range is never clipped: the caller chooses it). */
+int egdst_simulate_batch_spec_lag(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
+                                  long long nrand, unsigned long long seed, int rndtype,
+                                  const egdst_moment_lag *spec, int nmom,
+                                  const double *target /* [nmom] */, const double *W /* [nmom x nmom] row-major */,
+                                  double *means_dev /* [ndraw][nmom] */, int *counts_dev /* [ndraw][nmom] */,
+                                  double *obj_dev /* [ndraw] */);
 /* Uniform number k of stream `seed` (host replay of the device generator): with z = seed + (k+1)*0x9E3779B97F4A7C15,
  * z = (z ^ z>>30)*0xBF58476D1CE4E5B9, z = (z ^ z>>27)*0x94D049BB133111EB, z ^= z>>31 (splitmix64): (z >> 11) * 2^-53. */
 double egdst_uniform(unsigned long long seed, unsigned long long k);
