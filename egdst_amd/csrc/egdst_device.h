@@ -43,6 +43,7 @@ struct Batch {
     int *negflag;        // [(draw*MS_NST+ist)*MS_ND+id] a grid point of the stream signalled c1<=0 (set by k_grid)
     int *fixn;           // [MAX_GROUPS * nt] streams listed for k_fixup per (group, period)
     int *fixlist;        // [ndraw*MS_NST*MS_ND] the lists, a group's at its first slot
+    int *tickets;        // [3][MAX_GROUPS * nt] next entry to take of a (group, period)'s k_fixup, k_envelope pass 3 and k_tp_big list (eg_take_ticket)
     unsigned *work;      // [ndraw] re-basing calls of the draw's guess streams in this solve (straggler detection)
     int sorted_valid;    // != 0: k_sortcheck runs before the kernels of every period and stamps tsorted[cell] with sorted_valid + it
                          // when the next-period table of the cell is NOT in order (eg_tab_sorted); the base differs from solve to solve

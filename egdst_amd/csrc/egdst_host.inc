@@ -16,10 +16,18 @@ struct Env1Tile { unsigned long long desc, evals; };
 #endif
 #define EG_GRID_SAMPLED_ROWS 2048  // LDS rows of k_grid_lds' sampled index (tables too long to stage whole)
 #define EG_NPROF 9      // kernel classes of egdst_get_profile
-#define EG_FIX_GRID 32  // workgroups of a k_fixup launch; they loop over the streams k_fixup_scan listed
+// The list-driven launches of a period (k_fixup, k_tp_big, k_envelope pass 3): workgroups per EG_SPARSE_REF_CELLS cells of the
+// group, never fewer than that many and never more than the cap (LaunchPlan, eg_sparse_grid).  The numbers per 256 cells are what
+// was tuned with 16 groups of 256 draws of C2 (one cell per draw); a group of 1024 to 2048 draws has lists four to eight times as long.
+#define EG_SPARSE_REF_CELLS 256
+#define EG_FIX_GRID 32  // k_fixup; its workgroups take the streams k_fixup_scan listed by ticket
+#define EG_FIX_GRID_MAX 512       // (two workgroups per CU, FIX_MINW)
 #define EG_ENV_TP_MIN_CELLS 512   // (draw, state) cells per solve from which the throughput path of the envelope step is used
-#define EG_ENV_TP_REST_GRID 32    // workgroups of the k_envelope launch that does the cells the throughput path left over
-#define EG_ENV_TP_BIG_GRID 64     // workgroups of the second-tier launch of stage 1 (k_tp_big)
+#define EG_ENV_TP_REST_GRID 32    // the k_envelope launch that does the cells the throughput path left over (pass 3)
+#define EG_ENV_TP_BIG_GRID 64     // the second-tier launch of stage 1 (k_tp_big)
+#define EG_ENV_TP_GRID_MAX 256    // (both hold most of a CU's LDS: one workgroup per CU)
+// -DEG_SPARSE_GRID_MAX=n (checking builds): at most n workgroups for each of the three, so that a test's lists are many times
+// longer than its launches are wide.  Default: no cap.
 #define EG_ENV_TP_MAX_KEYS 5120   // points of a stream that the kernels of the throughput path keep in LDS (k_tp_walk: 24 B each)
 #ifndef EG_TP_WALK_BS0
 #define EG_TP_WALK_BS0 TP_WALK_BS  // threads of a stage-0 walk workgroup
@@ -49,6 +57,8 @@ struct LaunchPlan {
     int tp_lkcap, tp_lkcap0, tp_scap0, tp_scap1, tp_bigcap;  // stream budgets of the throughput path's kernels
     bool tp_big;         // second tier of stage 1 (k_tp_big)
     int tp_walk_bs0;     // threads of a stage-0 walk workgroup
+    int fix_wg, tp_big_wg, tp_rest_wg;              // workgroups per EG_SPARSE_REF_CELLS cells of a group: k_fixup, k_tp_big, k_envelope pass 3
+    int fix_wg_max, tp_big_wg_max, tp_rest_wg_max;  // and the most of each (eg_sparse_grid)
 };
 struct egdst_handle {
     Batch b;
@@ -95,7 +105,8 @@ struct egdst_handle {
     unsigned *work_h;
     unsigned char *strag_h;         // [ndraw] 1 = currently scheduled as a straggler
     int nstrag, adaptive, hwq;
-    hipStream_t gstream[EGDST_MAX_GROUPS];
+    int auto_groups;                // ngroups is the library's own choice, revisited after every solve (eg_history_groups)
+    hipStream_t gstream[EGDST_MAX_GROUPS];   // of groups 1 ..; group 0 runs on `stream`
     hipEvent_t fork_ev, join_ev[EGDST_MAX_GROUPS];
 };
 
@@ -320,7 +331,50 @@ static LaunchPlan plan_launches(const Geom &g, const Options &o)
     // threads of a stage-0 walk workgroup (all load the stream, its waves walk segments of it); stage 1 uses TP_WALK_BS
     p.tp_walk_bs0 = (EG_TP_WALK_BS0 < WAVE || EG_TP_WALK_BS0 > TP_WALK_BS || EG_TP_WALK_BS0 % WAVE) ? TP_WALK_BS : EG_TP_WALK_BS0;
 #endif
+    p.fix_wg = EG_FIX_GRID, p.fix_wg_max = EG_FIX_GRID_MAX;
+    p.tp_big_wg = EG_ENV_TP_BIG_GRID, p.tp_rest_wg = EG_ENV_TP_REST_GRID;
+    p.tp_big_wg_max = p.tp_rest_wg_max = EG_ENV_TP_GRID_MAX;
     return p;
+}
+
+// Workgroups of a list-driven launch of a group with `cells` cells whose list holds at most `entries`: `per_ref` per
+// EG_SPARSE_REF_CELLS cells (at least that many: the small groups keep what they had), at most `most`.  A workgroup that finds
+// the list exhausted leaves at once.
+static unsigned eg_sparse_grid(unsigned cells, unsigned entries, int per_ref, int most)
+{
+    unsigned n = (unsigned)(((unsigned long long)cells * (unsigned)per_ref + EG_SPARSE_REF_CELLS - 1) / EG_SPARSE_REF_CELLS);
+    if (n < (unsigned)per_ref) n = (unsigned)per_ref;
+    if (n > (unsigned)most) n = (unsigned)most;
+#ifdef EG_SPARSE_GRID_MAX
+    if (n > (unsigned)(EG_SPARSE_GRID_MAX)) n = (unsigned)(EG_SPARSE_GRID_MAX);
+#endif
+    return n < entries ? n : entries;
+}
+
+// Regular groups of a handle.  Group 0 runs on the handle's stream and every other group on a stream of its own.  The runtime gives
+// a stream a hardware queue of its own while it has made fewer than GPU_MAX_HW_QUEUES of them; a stream that comes after that shares
+// a queue with an earlier one, which one is not ours to say, and the null stream has a queue in nearly every process (hipMemcpy uses
+// it): the queues that can each run one chain of a solve are those beside the null stream's.
+static int eg_chain_queues(int hwq) { return hwq > 1 ? hwq - 1 : 1; }
+// At create.  Ten queues or more: the counts measured with 24 (DESIGN.md section 5).  Fewer: 4 groups from 1024 cells, whatever the
+// queues -- batches whose kernels fill the GPU (C5 x 128, C2 with a0 = 0) lose little where two of their groups share a queue and
+// more with a group fewer (4 queues: 3.58 against 3.88 s, 181 against 193 ms).
+static int eg_default_groups(int hwq, long cells)
+{
+    if (hwq >= 10) return cells >= 1024 && hwq >= 20 ? 16 : (cells >= 512 ? 8 : (cells >= 64 ? 4 : 1));
+    return cells >= 1024 ? 4 : 1;
+}
+// After a solve (egdst_sync, while the count is the library's own and history-based scheduling is on).  A chain that is mostly
+// list-driven launches -- a few workgroups, each a long sequential stretch -- fills nothing, and two such chains on one queue run end
+// to end: C2 x 4096 with a0 = -5 on 4 queues, 273 ms with 4 groups against 176 with 3.  Such a handle gets no more groups than chain
+// queues.  The measure is the share of the guess streams that k_fixup regenerated in the solve, on handles whose envelope step takes the
+// throughput path (the others have no list-driven launch besides k_fixup): 1.4 % on that batch, 0.16 % with a0 = 0; the line is drawn
+// between the two at their geometric mean.
+#define EG_SPARSE_HEAVY_SHARE 0.005
+static int eg_history_groups(int hwq, long cells, bool env_tp, double regen_share)
+{
+    const int g = eg_default_groups(hwq, cells), q = eg_chain_queues(hwq);
+    return (env_tp && regen_share >= EG_SPARSE_HEAVY_SHARE && g > q) ? q : g;
 }
 
 extern "C" int egdst_create(const egdst_desc *d, int ndraw, int keep_history, void *stream, egdst_handle **out)
@@ -410,6 +464,7 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
         {(void **)&b.order, sizeof(int) * ndraw}, {(void **)&b.work, sizeof(unsigned) * ndraw},
         {(void **)&b.nregen, sizeof(unsigned) * ndraw},
         {(void **)&b.fixn, sizeof(int) * EGDST_MAX_GROUPS * g.nt}, {(void **)&b.fixlist, sizeof(int) * nds * MS_ND},
+        {(void **)&b.tickets, sizeof(int) * 3 * EGDST_MAX_GROUPS * g.nt},
         {(void **)&b.negflag, sizeof(int) * nds * MS_ND}, {(void **)&b.tsorted, sizeof(int) * nds},
         {(void **)&b.secn, sizeof(int) * nds * MS_ND}, {(void **)&b.secact, sizeof(int) * nds * MS_ND},
         {(void **)&b.secerr, sizeof(int) * nds * MS_ND}, {(void **)&b.secev, sizeof(double) * nds * MS_ND},
@@ -488,11 +543,8 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
     h->ngroups = 1;
     {
         const int hwq = h->opt.hwq.value_or(4);  // (the HIP runtime's default)
-        // measured on MI355X (DESIGN.md §5): 8 groups need their own hardware queues to pay off
         const long cells = (long)ndraw * MS_NST;  // k_envelope workgroups per period
-        int want = h->opt.groups ? *h->opt.groups
-                                 : (hwq >= 10 ? (cells >= 1024 && hwq >= 20 ? 16 : (cells >= 512 ? 8 : (cells >= 64 ? 4 : 1)))
-                                              : (cells >= 1024 ? 4 : 1));
+        int want = h->opt.groups ? *h->opt.groups : eg_default_groups(hwq, cells);
         h->hwq = hwq;
         h->adaptive = h->opt.adaptive.value_or(1);
         h->order_h = (int *)malloc(sizeof(int) * ndraw);
@@ -503,6 +555,7 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
             egdst_destroy(h);
             return rc_;
         }
+        h->auto_groups = !h->opt.groups;
     }
     // quadrature: weights as given, abscissae through the inverse normal cdf (egdst_solver.c:162-164)
     double *q = (double *)malloc(sizeof(double) * 2 * g.ny);
@@ -523,23 +576,25 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
     return 0;
 }
 
-// Lay the draws out over the groups: the regular draws in index order, split evenly over the regular groups; the
-// stragglers after them, on lanes of their own while hardware queues are left (one stream each needs one), otherwise
-// dealt out over the regular groups.  Uploads the slot -> draw table on the handle's stream.
+// Streams and join events of groups 1 .. n-1 (regular groups and straggler lanes).  Group 0 runs on the handle's own stream, which
+// would otherwise sit idle, with a hardware queue behind it, from the fork to the join.
 static int ensure_group_streams(egdst_handle *h, int n)
 {
     if (!h->fork_ev) HIPCHK(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
-    for (int g = 0; g < n; g++) {
+    for (int g = 1; g < n; g++) {
         if (!h->gstream[g]) HIPCHK(hipStreamCreateWithFlags(&h->gstream[g], hipStreamNonBlocking));
         if (!h->join_ev[g]) HIPCHK(hipEventCreateWithFlags(&h->join_ev[g], hipEventDisableTiming));
     }
     return 0;
 }
 
+// Lay the draws out over the groups: the regular draws in index order, split evenly over the regular groups; the
+// stragglers after them, on lanes of their own while hardware queues are left (one stream each needs one), otherwise
+// dealt out over the regular groups.  Uploads the slot -> draw table on the handle's stream.
 static int build_schedule(egdst_handle *h)
 {
     const int nd = h->b.g.ndraw, G = h->ngroups;
-    int spare = (h->hwq - 2) - G;  // hardware queues not taken by the regular groups, the caller's and the null stream
+    int spare = eg_chain_queues(h->hwq) - G;  // hardware queues not taken by the regular groups (group 0: the handle's stream) and the null stream
     if (spare > EGDST_MAX_GROUPS - G) spare = EGDST_MAX_GROUPS - G;
     if (spare > 8) spare = 8;
     const int lanes = (G > 1 && h->nstrag > 0 && spare > 0) ? (h->nstrag < spare ? h->nstrag : spare) : 0;
@@ -616,12 +671,8 @@ extern "C" int egdst_set_groups(egdst_handle *h, int ngroups)
     if (ngroups > EGDST_MAX_GROUPS) ngroups = EGDST_MAX_GROUPS;
     if (ngroups > h->b.g.ndraw) ngroups = h->b.g.ndraw;
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (!h->fork_ev) HIPCHK(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
-    for (int g = 0; g < ngroups; g++) {
-        if (!h->gstream[g]) HIPCHK(hipStreamCreateWithFlags(&h->gstream[g], hipStreamNonBlocking));
-        if (!h->join_ev[g]) HIPCHK(hipEventCreateWithFlags(&h->join_ev[g], hipEventDisableTiming));
-    }
     h->ngroups = ngroups;
+    h->auto_groups = 0;  // (the caller's choice stands)
     memset(h->strag_h, 0, h->b.g.ndraw);
     h->nstrag = 0;
     return build_schedule(h);
@@ -752,6 +803,9 @@ static int batch_for_call(egdst_handle *h, const Batch **out)
     return 0;
 }
 
+// The ticket of a list-driven launch (eg_take_ticket): which = 0 k_fixup, 1 k_envelope pass 3, 2 k_tp_big.
+static int *eg_ticket(const Batch &b, int which, int gi, int it) { return b.tickets + ((size_t)which * EGDST_MAX_GROUPS + gi) * b.g.nt + it; }
+
 // One group's launches of one period: its stream, its device copy of the Batch and its range of the schedule.
 struct GroupStep {
     egdst_handle *h;
@@ -829,15 +883,16 @@ static void enqueue_envelope(const GroupStep &s, int terminal, bool env_tp, bool
         hipLaunchKernelGGL(k_env1, dim3(e1_nb, nc), dim3(E1_BS), 0, s.gs, s.bg, it, terminal, b.e1tiles, b.e1done, e1_nb, (unsigned)(it + 1),
                            p.e1_defer_all);
         hipLaunchKernelGGL(k_envelope, dim3(nc), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 1, 0, (const int *)nullptr,
-                           (const int *)nullptr);
+                           (const int *)nullptr, (int *)nullptr);
     } else
         hipLaunchKernelGGL(k_envelope, dim3(nc), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 2, 0, (const int *)nullptr,
-                           (const int *)nullptr);
+                           (const int *)nullptr, (int *)nullptr);
     eg_end(s, 2);
 #else
     if (env_tp && !terminal) {
         int *tcnt = b.tpn + (size_t)s.gi * b.g.nt + it, *tlist = b.tplist + (size_t)s.draw0 * MS_NST;
         int *bigc = b.tpbign + (size_t)s.gi * b.g.nt + it, *bigl = b.tpbiglist + (size_t)s.draw0 * MS_NST;
+        int *rest_tk = eg_ticket(b, 1, s.gi, it), *big_tk = eg_ticket(b, 2, s.gi, it);
         eg_before(s, 4);
         hipLaunchKernelGGL(k_tp_prep, dim3(nc * MS_ND), dim3(TP_BS), 0, s.gs, s.bg, it);
         eg_end(s, 4);
@@ -857,28 +912,29 @@ static void enqueue_envelope(const GroupStep &s, int terminal, bool env_tp, bool
         hipLaunchKernelGGL(k_tp_walk, dim3(nc), dim3(TP_WALK_BS), (size_t)EG_TP_WALK_LDS_PER_POINT * p.tp_lkcap, s.gs, s.bg, it, 1, tlist, tcnt,
                            p.tp_lkcap);
         if (p.tp_big) {
-            const unsigned ng = nc < (unsigned)EG_ENV_TP_BIG_GRID ? nc : (unsigned)EG_ENV_TP_BIG_GRID;
+            const unsigned ng = eg_sparse_grid(nc, nc, p.tp_big_wg, p.tp_big_wg_max);
             const size_t walk_lds = (size_t)EG_TP_WALK_LDS_PER_POINT * p.tp_bigcap;
             const size_t lds = tp_sort_lds(p.tp_bigcap) > walk_lds ? tp_sort_lds(p.tp_bigcap) : walk_lds;
             hipLaunchKernelGGL(k_tp_big, dim3(ng), dim3(TP_SORT_BS), lds, s.gs, s.bg, it, tlist, tcnt, p.tp_bigcap, (const int *)bigl,
-                               (const int *)bigc);
+                               (const int *)bigc, big_tk);
         }
         eg_end(s, 8);
         eg_before(s, 2);
-        hipLaunchKernelGGL(k_envelope, dim3(nc < (unsigned)EG_ENV_TP_REST_GRID ? nc : (unsigned)EG_ENV_TP_REST_GRID), dim3(ENV_MAXBS),
-                           h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 3, 0, (const int *)tlist, (const int *)tcnt);
+        // (after k_tp_big, which appends the cells it gives up on to this launch's list)
+        hipLaunchKernelGGL(k_envelope, dim3(eg_sparse_grid(nc, nc, p.tp_rest_wg, p.tp_rest_wg_max)), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it,
+                           terminal, h->lcap, 3, 0, (const int *)tlist, (const int *)tcnt, rest_tk);
         eg_end(s, 2);
         return;
     }
     eg_before(s, 2);
     if (env_parts) {
         hipLaunchKernelGGL(k_envelope, dim3(nc * MS_ND), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 2, 1,
-                           (const int *)nullptr, (const int *)nullptr);
+                           (const int *)nullptr, (const int *)nullptr, (int *)nullptr);
         hipLaunchKernelGGL(k_envelope, dim3(nc), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 2, 2, (const int *)nullptr,
-                           (const int *)nullptr);
+                           (const int *)nullptr, (int *)nullptr);
     } else
         hipLaunchKernelGGL(k_envelope, dim3(nc), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it, terminal, h->lcap, 2, 0, (const int *)nullptr,
-                           (const int *)nullptr);
+                           (const int *)nullptr, (int *)nullptr);
     eg_end(s, 2);
     // (Measured and removed in round 4: a SLOW LANE per group -- the cells whose guess streams k_fixup has to regenerate, 3 % of the
     //  cells of a C2 a0 = -5 period and 57 of the 172 ms of every group's chain (the regeneration itself, and the secondary envelope of a
@@ -914,6 +970,7 @@ static int enqueue_solve(egdst_handle *h)
     HIPCHK(hipMemsetAsync(b.fixn, 0, sizeof(int) * EGDST_MAX_GROUPS * g.nt, s));
     HIPCHK(hipMemsetAsync(b.tpn, 0, sizeof(int) * EGDST_MAX_GROUPS * g.nt, s));
     HIPCHK(hipMemsetAsync(b.tpbign, 0, sizeof(int) * EGDST_MAX_GROUPS * g.nt, s));
+    HIPCHK(hipMemsetAsync(b.tickets, 0, sizeof(int) * 3 * EGDST_MAX_GROUPS * g.nt, s));
     HIPCHK(hipMemsetAsync(b.tpstat, 0, sizeof(unsigned) * 2 * g.ndraw, s));
 #if MS_ND == 1
     // k_env1: descriptors carry the period as their tag, valid within one solve; the counters count on from zero
@@ -930,9 +987,9 @@ static int enqueue_solve(egdst_handle *h)
         }
         HIPCHK(hipMemcpyAsync(h->b_dev, h->b_host, sizeof(Batch) * G, hipMemcpyHostToDevice, s));
     }
-    if (G > 1) {  // fork: the groups start after everything enqueued on the handle's stream so far
+    if (G > 1) {  // fork: groups 1 .. start after everything enqueued on the handle's stream so far; group 0 follows on that stream itself
         HIPCHK(hipEventRecord(h->fork_ev, s));
-        for (int gi = 0; gi < G; gi++) HIPCHK(hipStreamWaitEvent(h->gstream[gi], h->fork_ev, 0));
+        for (int gi = 1; gi < G; gi++) HIPCHK(hipStreamWaitEvent(h->gstream[gi], h->fork_ev, 0));
     }
     // the kink log (egdst_set_dbgout, which may be called after create) orders its rows per cell: one workgroup per cell
     const bool env_tp = p.env_tp && !b.klog, env_parts = p.env_parts && !b.klog;
@@ -946,7 +1003,7 @@ static int enqueue_solve(egdst_handle *h)
             const int draw0 = (G > 1) ? h->gstart[gi] : 0;
             const int gdraws = ((G > 1) ? h->gstart[gi + 1] : g.ndraw) - draw0;
             if (gdraws <= 0) continue;
-            const GroupStep st = {h, gi, it, (G > 1) ? h->gstream[gi] : s, h->b_dev + gi, draw0, gdraws};  // (b_dev: uploaded above)
+            const GroupStep st = {h, gi, it, gi ? h->gstream[gi] : s, h->b_dev + gi, draw0, gdraws};  // (b_dev: uploaded above)
             const int combos = gdraws * MS_NST * MS_ND;
             if (it == g.nt - 1) {
                 eg_before(st, 0);
@@ -970,16 +1027,16 @@ static int enqueue_solve(egdst_handle *h)
             eg_before(st, 3);
             int *cnt = b.fixn + (size_t)gi * g.nt + it, *list = b.fixlist + (size_t)draw0 * MS_NST * MS_ND;
             hipLaunchKernelGGL(k_fixup_scan, dim3(combos), dim3(WAVE), 0, st.gs, st.bg, it, cnt, list);
-            hipLaunchKernelGGL(k_fixup, dim3(combos < EG_FIX_GRID ? combos : EG_FIX_GRID), dim3(FIX_BS), 0, st.gs, st.bg, it, (const int *)cnt,
-                               (const int *)list);
+            hipLaunchKernelGGL(k_fixup, dim3(eg_sparse_grid((unsigned)(gdraws * MS_NST), (unsigned)combos, p.fix_wg, p.fix_wg_max)), dim3(FIX_BS), 0,
+                               st.gs, st.bg, it, (const int *)cnt, (const int *)list, eg_ticket(b, 0, gi, it));
             eg_end(st, 3);
             eg_after(st, "k_grid+k_fixup");
             enqueue_envelope(st, 0, env_tp, env_parts);
             eg_after(st, "k_envelope");
         }
     }
-    if (G > 1)  // join: the handle's stream continues when every group is done
-        for (int gi = 0; gi < G; gi++) {
+    if (G > 1)  // join: the handle's stream, group 0's launches on it, continues when every other group is done
+        for (int gi = 1; gi < G; gi++) {
             HIPCHK(hipEventRecord(h->join_ev[gi], h->gstream[gi]));
             HIPCHK(hipStreamWaitEvent(s, h->join_ev[gi], 0));
         }
@@ -1009,6 +1066,19 @@ extern "C" int egdst_sync(egdst_handle *h)
         for (int i = 0; i < h->b.g.ndraw && !rc; i++)
             if (st[i]) rc = set_err(st[i], "draw %d: %s", i, egdst_strerror(st[i]));
     free(st);
+    int regrouped = 0;
+    const long cells = (long)h->b.g.ndraw * MS_NST;
+    if (h->adaptive && h->auto_groups && e == hipSuccess && h->b.g.nt > 1 &&
+        eg_default_groups(h->hwq, cells) > eg_chain_queues(h->hwq)) {  // (only then can the history change the count)
+        unsigned *nr = (unsigned *)malloc(sizeof(unsigned) * h->b.g.ndraw);
+        if (hipMemcpy(nr, h->b.nregen, sizeof(unsigned) * h->b.g.ndraw, hipMemcpyDeviceToHost) == hipSuccess) {
+            double sum = 0;
+            for (int i = 0; i < h->b.g.ndraw; i++) sum += nr[i];
+            const int want = eg_history_groups(h->hwq, cells, h->plan.env_tp, sum / ((double)cells * MS_ND * (h->b.g.nt - 1)));
+            if (want != h->ngroups) h->ngroups = want, regrouped = 1;
+        }
+        free(nr);
+    }
     if (h->adaptive && h->ngroups > 1 && e == hipSuccess) {
         // Stragglers: draws whose guess streams re-based more than EG_STRAGGLER_CALLS times in this solve (a normal
         // stream re-bases a few dozen times, a degenerate one ~9000 times in one period, strictly sequentially).
@@ -1023,11 +1093,16 @@ extern "C" int egdst_sync(egdst_handle *h)
                 ns += sl;
             }
             h->nstrag = ns;
-            if (changed) {
+            if (changed || regrouped) {
                 const int rc2 = build_schedule(h);
                 if (rc2 && !rc) rc = rc2;
             }
+            regrouped = 0;
         }
+    }
+    if (regrouped) {
+        const int rc2 = build_schedule(h);
+        if (rc2 && !rc) rc = rc2;
     }
     return rc;
 }

@@ -1090,11 +1090,30 @@ __global__ void __launch_bounds__(WAVE) k_fixup_scan(const Batch *bp_, int it, i
 #ifndef FIX_MINW
 #define FIX_MINW 2  // two workgroups per CU (<= 256 VGPRs); (3: at most 168 VGPRs, a k_fixup wave beside two waves of the -DENV_MINW=3 k_envelope)
 #endif
-__global__ void __launch_bounds__(FIX_BS, FIX_MINW) k_fixup(const Batch *bp_, int it, const int *cnt, const int *list)
+// The list-driven launches (k_fixup, k_tp_big, k_envelope pass 3): a workgroup takes its next list entry from the launch's
+// ticket (one per (group, period) and kernel, beside the list's counter and cleared with it once per solve) instead of striding
+// by gridDim.x, so a slow entry holds up the workgroup that has it and nothing else.  The entries are independent and the lists'
+// order is whatever eg_list_push made it, so nothing depends on who takes which.  `sh`: one int of LDS; both barriers are
+// reached by every thread of the workgroup (the second: thread 0 may not draw again while another still reads).
+static __device__ __forceinline__ int eg_take_ticket(int *ticket, int *sh)
+{
+    if (threadIdx.x == 0) *sh = atomicAdd(ticket, 1);
+    __syncthreads();
+    int k = *sh;
+    __syncthreads();
+#ifndef EGDST_EMU
+    k = __builtin_amdgcn_readfirstlane(k);  // (uniform, as the block index it replaces was)
+#endif
+    return k;
+}
+
+__global__ void __launch_bounds__(FIX_BS, FIX_MINW) k_fixup(const Batch *bp_, int it, const int *cnt, const int *list, int *ticket)
 {
     BatchRef b = EG_BATCH_REF(bp_);
+    __shared__ int tk;
     const int n = min(*cnt, b.gdraws * MS_NST * MS_ND);
-    for (int k = blockIdx.x; k < n; k += gridDim.x) {
+    if (n <= 0) return;  // (an empty list: no ticket drawn)
+    for (int k; (k = eg_take_ticket(ticket, &tk)) < n;) {
         const int combo = list[k];
         const int id = combo % MS_ND, ist = (combo / MS_ND) % MS_NST, draw = b.order[b.draw0 + combo / (MS_ND * MS_NST)];
 #ifdef EGDST_EMU
@@ -3454,16 +3473,22 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
 
 // pass 0 / 1 / 2: one workgroup per job of the launch.  pass 3: the cells the throughput path (k_tp_*, below) left to this
 // kernel -- `list` holds their slots, *cnt how many; a small grid loops over them, so that a period with no such cell costs
-// a handful of workgroups that return at once instead of one 125-KB-LDS workgroup per cell of the group.
+// a handful of workgroups that return at once instead of one 125-KB-LDS workgroup per cell of the group.  They take the
+// list's entries by ticket (eg_take_ticket; `ticket` is read in pass 3 only).
 __global__ void __launch_bounds__(ENV_MAXBS, ENV_MINW) ENV_VGPR_ATTR k_envelope(const Batch *bp_, int it, int terminal, int lcap, int pass, int part,
-                                                                                const int *list, const int *cnt)
+                                                                                const int *list, const int *cnt, int *ticket)
 {
     BatchRef b = EG_BATCH_REF(bp_);
+    __shared__ int tk;
     // (ONE inlined copy of the cell's code: the other passes are the loop with a single turn)
     const int n = (pass == 3) ? min(*cnt, b.gdraws * MS_NST) : (int)gridDim.x;
-    for (int k = blockIdx.x; k < n; k += gridDim.x) {
+    if (n <= 0) return;  // (pass 3 with an empty list: no ticket drawn)
+    for (int k = blockIdx.x;;) {
+        if (pass == 3) k = eg_take_ticket(ticket, &tk);
+        if (k >= n) break;
         eg_envelope_cell(b, it, terminal, lcap, pass == 3 ? 1 : pass, part, pass == 3 ? list[k] : k);
         __syncthreads();  // (the LDS of the cell is reused by the next one)
+        if (pass != 3) break;
     }
 }
 
@@ -4179,12 +4204,14 @@ __global__ void __launch_bounds__(TP_WALK_BS, TP_WALK_MINW) k_tp_walk(const Batc
 // kernel latencies and launch gaps, ~110 us, on every group's chain every period for a handful of cells (tests/diag/gpu_group_finish.py).
 // TP_SORT_BS threads: the sort's size; the walk loads with all of them and walks with up to four waves as it does elsewhere.
 __global__ void __launch_bounds__(TP_SORT_BS, TP_WALK_MINW) k_tp_big(const Batch *bp_, int it, int *list, int *cnt, int cap, const int *biglist,
-                                                                     const int *bigcnt)
+                                                                     const int *bigcnt, int *ticket)
 {
     EG_DYN_LDS(dynlds);
     __shared__ TpShared S;
+    __shared__ int tk;
     const int n = min(*bigcnt, EG_BATCH_REF(bp_).gdraws * MS_NST);
-    for (int k = blockIdx.x; k < n; k += gridDim.x) {
+    if (n <= 0) return;  // (an empty list: no ticket drawn)
+    for (int k; (k = eg_take_ticket(ticket, &tk)) < n;) {
         tp_sort(EG_BATCH_REF(bp_), it, 1, cap, cap, biglist[k], &S, (double *)dynlds, 1);
         __threadfence_block();  // (the sorted stream goes through global memory from one phase to the next)
         __syncthreads();

@@ -101,15 +101,20 @@ int egdst_create_compact(const egdst_desc *desc, int ndraw, int keep_history, in
                          egdst_handle **out);
 int egdst_destroy(egdst_handle *h);
 /* Draw groups.  The draws of a handle are split into `ngroups` contiguous ranges whose per-period kernels are
- * enqueued on separate HIP streams (forked from and joined to the handle's stream), so that one draw with a long
- * sequential stretch -- the reference's guess generator re-bases point after point on some parameter draws --
- * holds up its own group only.  Results do not depend on the grouping.  Default with GPU_MAX_HW_QUEUES >= 10: 4 groups from
- * 64 (draw, state) cells, 8 from 512, and 16 from 1024 cells with >= 20 queues; with the runtime's default of 4
- * hardware queues: 4 groups from 1024 cells (environment EGDST_GROUPS overrides).  At most 32, and at most ndraw. */
+ * enqueued on separate HIP streams, so that one draw with a long sequential stretch -- the reference's guess generator
+ * re-bases point after point on some parameter draws -- holds up its own group only.  Group 0 is enqueued on the handle's own
+ * stream, groups 1 .. ngroups-1 on streams forked from and joined to it: ngroups groups keep ngroups hardware queues busy.
+ * Results do not depend on the grouping.  The library reads GPU_MAX_HW_QUEUES (unset: 4, the HIP runtime's default) and never
+ * sets it.  Default with >= 10 queues: 4 groups from 64 (draw, state) cells, 8 from 512, and 16 from 1024 cells with >= 20
+ * queues; with fewer queues: 4 groups from 1024 cells.  Two groups on one queue run one behind the other and the null stream
+ * holds a queue, which costs a batch of mostly sparse launches dearly and a dense one little: while the count is the default
+ * and history-based scheduling is on, a handle on the envelope step's throughput path whose last solve regenerated 0.5 % or more
+ * of its guess streams continues with at most queues - 1 groups (3 on 4 queues), and returns to the default when a solve falls
+ * below.  Environment EGDST_GROUPS and a call of this function override and end that.  At most 32, and at most ndraw. */
 int egdst_set_groups(egdst_handle *h, int ngroups);
 /* History-based scheduling (on by default with more than one group): after a solve, the draws whose guess streams
  * re-based more than 1000 times (degenerate parameter draws: one such stream is ~75 ms of strictly sequential work)
- * are scheduled on up to 8 extra streams of their own in the next solves, as far as hardware queues are left,
+ * are scheduled on up to 8 extra streams of their own in the next solves, as far as hardware queues are left beside the groups',
  * so that they hold up each other instead of a whole group.  Results do not depend on it. */
 int egdst_set_adaptive(egdst_handle *h, int on);
 /* Current schedule: regular groups, extra straggler lanes, draws currently treated as stragglers. */
