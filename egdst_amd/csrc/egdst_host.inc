@@ -81,6 +81,8 @@ struct egdst_handle {
     egdst_moment_lag *sim_spec; // estimation_step: the moment records (egdst_simulate_batch_spec[_lag]), the target and the weighting
     double *sim_tgt, *sim_W;    // matrix, or its diagonal (egdst_simulate_batch_moments)
     size_t sim_spec_bytes, sim_tgt_bytes, sim_W_bytes;
+    double *sim_scores;         // egdst_simulate_batch_spec_cov: the per-agent scores of a slice of draws, [nd][nsim][cov_padded(nmom)]
+    size_t sim_scores_bytes;
     size_t klog_bytes;  // kink log (egdst_set_dbgout), allocated apart from the pool
     void **emu_items;  // sanitizer harness only: one heap block per array instead of the pool
     int emu_nitems;
@@ -733,7 +735,7 @@ extern "C" int egdst_destroy(egdst_handle *h)
     if (h->b.kcnt) (void)hipFree(h->b.kcnt);
     {
         void *simbufs[] = {h->sim_init, h->sim_rs, h->sim_sims, h->sim_means, h->sim_err, h->sim_counts,
-                           h->sim_spec, h->sim_tgt, h->sim_W};
+                           h->sim_spec, h->sim_tgt, h->sim_W, h->sim_scores};
         for (void *p : simbufs)
             if (p) (void)hipFree(p);
     }
@@ -1494,9 +1496,12 @@ extern "C" double egdst_uniform(unsigned long long seed, unsigned long long k) {
 // otherwise spec [nmom] (host; the device sees the one record type, egdst_moment_lag) and W [nmom x nmom].  Draws [d0, d0+nd) are simulated together as long as their paths fit
 // EG_SIM_SLICE_BYTES, and a slice is reduced on the handle's stream before the next one overwrites the paths
 // (run_simulation waits for its kernel).  Nothing but the objective and, if asked for, the moments is written for the caller.
+// cov_dev (egdst_simulate_batch_spec_cov only; needs spec): every slice also goes through k_moment_scores and k_moment_cov, which
+// writes the slice's matrices straight into cov_dev [ndraw][nmom][nmom]; the scores of a slice then count beside its paths
+// towards EG_SIM_SLICE_BYTES.  Without cov_dev the slices, the launches and the uploads are those of the step without it.
 static int estimation_step(egdst_handle *h, const double *init, int nsim, const double *randstream_dev, long long nrand,
                            unsigned long long seed, int rndtype, const egdst_moment_lag *spec, int nmom, const double *target,
-                           const double *W, double *means_dev, int *counts_dev, double *obj_dev)
+                           const double *W, double *means_dev, int *counts_dev, double *obj_dev, double *cov_dev)
 {
     const Geom &g = h->b.g;
     const size_t nW = spec ? (size_t)nmom * nmom : (size_t)nmom;
@@ -1517,10 +1522,15 @@ static int estimation_step(egdst_handle *h, const double *init, int nsim, const 
             if (q_last < 0) q_first = j;
             q_last = j;
         }
-    const size_t per_draw = sizeof(double) * (size_t)EG_NOUT * g.nt * nsim;
+    const size_t score_draw = cov_dev ? sizeof(double) * (size_t)nsim * cov_padded(nmom) : 0;   // (a draw's scores)
+    const size_t per_draw = sizeof(double) * (size_t)EG_NOUT * g.nt * nsim + score_draw;
     int slice = (int)(EG_SIM_SLICE_BYTES / (per_draw ? per_draw : 1));
     if (slice < 1) slice = 1;
     if (slice > g.ndraw) slice = g.ndraw;
+    if (cov_dev) {
+        rc = sim_reserve((void **)&h->sim_scores, &h->sim_scores_bytes, score_draw * slice);
+        if (rc) return rc;
+    }
     for (int d0 = 0; d0 < g.ndraw; d0 += slice) {
         const int nd = (g.ndraw - d0 < slice) ? g.ndraw - d0 : slice;
         rc = run_simulation(h, d0, nd, 1, init, nsim, nullptr, randstream_dev, nrand, seed, rndtype);
@@ -1532,6 +1542,15 @@ static int estimation_step(egdst_handle *h, const double *init, int nsim, const 
             hipLaunchKernelGGL(k_quantiles, dim3(q_last - q_first + 1, nd), dim3(QNT_BS), 0, h->stream, (const double *)h->sim_sims,
                                nsim, g.nt, (const egdst_moment_lag *)h->sim_spec, q_first, nmom, h->sim_means + (size_t)d0 * nmom,
                                h->sim_counts + (size_t)d0 * nmom);
+        if (cov_dev) {
+            const int ntile = cov_padded(nmom) / COV_T;
+            hipLaunchKernelGGL(k_moment_scores, dim3((unsigned)(((size_t)nsim * cov_padded(nmom) + MOM_BS - 1) / MOM_BS), nd), dim3(MOM_BS),
+                               0, h->stream, (const double *)h->sim_sims, nsim, g.nt, (const egdst_moment_lag *)h->sim_spec, nmom,
+                               (const double *)(h->sim_means + (size_t)d0 * nmom), (const int *)(h->sim_counts + (size_t)d0 * nmom),
+                               h->sim_scores);
+            hipLaunchKernelGGL(k_moment_cov, dim3(ntile * (ntile + 1) / 2, nd), dim3(COV_BS), 0, h->stream,
+                               (const double *)h->sim_scores, nsim, nmom, cov_dev + (size_t)d0 * nmom * nmom);
+        }
     }
     if (obj_dev)
         hipLaunchKernelGGL(k_moment_objective, dim3(g.ndraw), dim3(MOM_BS), 0, h->stream, (const double *)h->sim_means,
@@ -1555,12 +1574,13 @@ extern "C" int egdst_simulate_batch_moments(egdst_handle *h, const double *init,
     if (!h || (obj_dev && (!target || !weight)) || (!obj_dev && !means_dev))
         return set_err(EGDST_E_ARG, "egdst_simulate_batch_moments: bad arguments");
     return estimation_step(h, init, nsim, randstream_dev, nrand, seed, rndtype, nullptr, EG_NOUT * h->b.g.nt, target, weight,
-                           means_dev, counts_dev, obj_dev);
+                           means_dev, counts_dev, obj_dev, nullptr);
 }
 
 // The step with user-defined moments and a full weighting matrix: the objective is e' W e.  Every argument is checked before
 // anything is enqueued.  The device sees one record type, egdst_moment_lag; egdst_simulate_batch_spec promotes its
-// egdst_moment records with zero lags and `who` names the door in the messages.
+// egdst_moment records with zero lags and `who` names the door in the messages.  cov_dev: the door is
+// egdst_simulate_batch_spec_cov, which takes no quantile.
 static_assert(sizeof(egdst_moment) == 56, "egdst_moment is 6 ints and 4 doubles (the Python dtype mirrors it)");
 static_assert(sizeof(egdst_moment_lag) == 64 && offsetof(egdst_moment_lag, lag2) == 56 && offsetof(egdst_moment_lag, cond_lag) == 60,
               "egdst_moment_lag is egdst_moment and 2 ints (the Python dtype mirrors it)");
@@ -1572,13 +1592,15 @@ static bool lag_inside(int it_first, int it_last, int lag, int nt)
 
 static int checked_estimation_step(const char *who, egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
                                    long long nrand, unsigned long long seed, int rndtype, const egdst_moment_lag *spec, int nmom,
-                                   const double *target, const double *W, double *means_dev, int *counts_dev, double *obj_dev)
+                                   const double *target, const double *W, double *means_dev, int *counts_dev, double *obj_dev,
+                                   double *cov_dev = nullptr)
 {
     const int nout = EG_NOUT, nt = h->b.g.nt;
     for (int j = 0; j < nmom; j++) {
         const egdst_moment_lag &q = spec[j];
         const char *bad = nullptr;
         if (q.kind < 0 || q.kind > 3) bad = "kind is not 0, 1, 2 or 3";
+        else if (q.kind == 3 && cov_dev) bad = "a quantile has no covariance here";
         else if (q.kind == 3 && !(q.lo > 0.0 && q.lo < 1.0)) bad = "the p of a quantile (lo) is not inside (0, 1)";   // (NaN fails both)
         else if (q.col < 0 || q.col >= nout) bad = "col is outside the simulated columns";
         else if (q.col2 < 0 || q.col2 >= nout) bad = "col2 is outside the simulated columns";
@@ -1592,7 +1614,7 @@ static int checked_estimation_step(const char *who, egdst_handle *h, const doubl
         if (bad) return set_err(EGDST_E_ARG, "%s: moment %d: %s", who, j, bad);
     }
     return estimation_step(h, init, nsim, randstream_dev, nrand, seed, rndtype, spec, nmom, target, W, means_dev, counts_dev,
-                           obj_dev);
+                           obj_dev, cov_dev);
 }
 
 extern "C" int egdst_simulate_batch_spec(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
@@ -1622,6 +1644,20 @@ extern "C" int egdst_simulate_batch_spec_lag(egdst_handle *h, const double *init
     return checked_estimation_step("egdst_simulate_batch_spec_lag", h, init, nsim, randstream_dev, nrand, seed, rndtype, spec, nmom,
                                    target, W, means_dev, counts_dev, obj_dev);
 }
+
+// The step with the covariance of the moments: the records and the checks of egdst_simulate_batch_spec_lag, no objective, and
+// per draw the matrix k_moment_cov forms from the per-agent scores (include/egdst.h).
+extern "C" int egdst_simulate_batch_spec_cov(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
+                                             long long nrand, unsigned long long seed, int rndtype, const egdst_moment_lag *spec,
+                                             int nmom, double *means_dev, int *counts_dev, double *cov_dev)
+{
+    if (!h || !spec || nmom <= 0) return set_err(EGDST_E_ARG, "egdst_simulate_batch_spec_cov: bad arguments");
+    if (!cov_dev) return set_err(EGDST_E_ARG, "egdst_simulate_batch_spec_cov: cov_dev is NULL");
+    return checked_estimation_step("egdst_simulate_batch_spec_cov", h, init, nsim, randstream_dev, nrand, seed, rndtype, spec, nmom,
+                                   nullptr, nullptr, means_dev, counts_dev, nullptr, cov_dev);
+}
+
+extern "C" int egdst_cov_parts(void) { return COV_P; }
 
 // egdst_call.c:17-164.  The index checks of the gateway are done here, in row order, because an out-of-range index
 // turns the switch to -1 for the rest of the call (that row and every later one are NaN) and a wrong column count

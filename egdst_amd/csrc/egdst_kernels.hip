@@ -5056,6 +5056,113 @@ __global__ void __launch_bounds__(MOM_BS) k_moment_objective(const double *means
     if (tid == 0) obj[blockIdx.x] = empty ? NAN : acc;
 }
 
+// Covariance of the moments (egdst_simulate_batch_spec_cov, include/egdst.h): the tile of k_moment_cov.  A workgroup of COV_BS
+// threads owns COV_T x COV_T entries (j, k) of D'D; its COV_P waves are the contract's P partials, wave t taking the agents
+// i = t (mod COV_P), and each of the 64 lanes of a wave holds a COV_R x COV_R register block of the tile.  The score matrix of a
+// draw is [nsim][nmomp] doubles, nmomp = nmom rounded up to COV_T with zeros in the padding (k_moment_scores writes them), so a
+// tile's rows are read in full without a bounds check on the record.  COV_KC agents are staged per pass: 2 * COV_KC * COV_T
+// doubles of LDS (32 KiB), which then hold the COV_P partial tiles for the tree.  The harness runs the same geometry.
+#define COV_T 32    // records per tile side (tests/test_gpu_moment_cov.py takes its widths from this)
+#define COV_R 4     // a lane's register block is COV_R x COV_R
+#define COV_P 4     // partials = waves of the workgroup (egdst_cov_parts)
+#define COV_WAVE 64
+#define COV_BS (COV_P * COV_WAVE)
+#define COV_KC 64   // agents staged per pass
+static_assert(COV_P >= 1 && COV_P <= 256 && (COV_P & (COV_P - 1)) == 0, "the partials of the covariance are a power of two in [1, 256]");
+static_assert((COV_T / COV_R) * (COV_T / COV_R) == COV_WAVE, "the register blocks of a wave's lanes cover the tile once");
+static_assert(COV_KC % COV_P == 0, "a pass starts at an agent that is partial 0's");
+static_assert(2 * COV_KC * COV_T >= COV_P * COV_T * COV_T, "the partial tiles fit the staging buffers");
+
+static __host__ __device__ __forceinline__ int cov_padded(int nmom) { return (nmom + COV_T - 1) / COV_T * COV_T; }
+
+// Scores of one slice of draws: for agent i and record j, c = the agent's qualifying pairs, s = the sum of their values in
+// ascending period (from 0.0; kind 2 adds 1.0 or 0.0) and d = (s - m_j * c) / N_j with the mean and the count k_moments wrote:
+// one product, one difference, one quotient (an empty moment: NaN - falls out of m_j = NaN and 0 / 0).  scores [nd][nsim][nmomp],
+// the record the fastest index: the lanes of a wave read one or two agents' paths and write consecutive doubles.  Padding
+// columns j >= nmom are 0.0.  One thread per (agent, column); blockIdx.y is the draw of the launch.
+__global__ void __launch_bounds__(MOM_BS) k_moment_scores(const double *sims, int nsim, int nt, const egdst_moment_lag *spec, int nmom,
+                                                          const double *means, const int *counts, double *scores)
+{
+    const int nmomp = cov_padded(nmom);
+    const size_t e = (size_t)blockIdx.x * MOM_BS + threadIdx.x;
+    if (e >= (size_t)nsim * nmomp) return;
+    const int i = (int)(e / nmomp), j = (int)(e % nmomp);
+    double *out = scores + (size_t)blockIdx.y * nsim * nmomp + e;
+    if (j >= nmom) {
+        *out = 0.0;
+        return;
+    }
+    const egdst_moment_lag q = spec[j];
+    const size_t per_agent = (size_t)EG_NOUT * nt;
+    const double *p = sims + ((size_t)blockIdx.y * nsim + i) * per_agent;
+    double s = 0;
+    int c = 0;
+    for (int it = q.it_first; it <= q.it_last; it++) {
+        double x;
+        if (!eg_moment_term(p + (size_t)it * EG_NOUT, q, &x)) continue;
+        if (q.kind == 2) x = (x >= q.lo && x <= q.hi) ? 1.0 : 0.0;
+        s += x, c++;
+    }
+    const double m = means[(size_t)blockIdx.y * nmom + j];
+    const double prod = m * (double)c;
+    *out = (s - prod) / (double)counts[(size_t)blockIdx.y * nmom + j];
+}
+
+// Omega = D'D of one draw's scores, upper triangle in tiles: blockIdx.x counts the tile pairs (tj <= tk) row by row, blockIdx.y
+// the draws of the launch; cov [nd][nmom][nmom].  Per pass COV_KC score rows of the two record ranges go through LDS; wave t
+// then adds, for its agents i = t (mod COV_P) in ascending i, the rounded products d_ij * d_ik to its register blocks (no FMA:
+// the translation unit is built with -ffp-contract=off).  At the end the COV_P partial tiles meet in LDS and are combined by the
+// contract's tree, p[t] += p[t + o] for o = COV_P / 2 .. 1; entry (j, k) with j <= k is written to both (j, k) and (k, j), so the
+// mirror carries its bits.  No atomics, and every barrier is reached by the whole workgroup (the loop bounds are uniform).
+__global__ void __launch_bounds__(COV_BS) k_moment_cov(const double *scores, int nsim, int nmom, double *cov)
+{
+    __shared__ double sbuf[2 * COV_KC * COV_T];
+    double *const sa = sbuf, *const sb = sbuf + COV_KC * COV_T;
+    const int nmomp = cov_padded(nmom), ntile = nmomp / COV_T;
+    int tj = 0, rest = (int)blockIdx.x;   // row tj of the triangle holds the ntile - tj pairs (tj, tj .. ntile - 1)
+    while (rest >= ntile - tj) rest -= ntile - tj, tj++;
+    const int tk = tj + rest;
+    const int tid = threadIdx.x, wave = tid / COV_WAVE, lane = tid % COV_WAVE;
+    const int lj = lane / (COV_T / COV_R) * COV_R, lk = lane % (COV_T / COV_R) * COV_R;   // the lane's block inside the tile
+    scores += (size_t)blockIdx.y * nsim * nmomp;
+    cov += (size_t)blockIdx.y * nmom * nmom;
+    double acc[COV_R][COV_R];
+    for (int a = 0; a < COV_R; a++)
+        for (int b = 0; b < COV_R; b++) acc[a][b] = 0.0;
+    for (int i0 = 0; i0 < nsim; i0 += COV_KC) {
+        const int rows = nsim - i0 < COV_KC ? nsim - i0 : COV_KC;
+        for (int e = tid; e < rows * COV_T; e += COV_BS) {   // (row e / COV_T of the pass, column e % COV_T of the tile)
+            const double *row = scores + (size_t)(i0 + e / COV_T) * nmomp + e % COV_T;
+            sa[e] = row[tj * COV_T];
+            sb[e] = row[tk * COV_T];
+        }
+        __syncthreads();
+        for (int c = wave; c < rows; c += COV_P) {   // (i0 is a multiple of COV_P: agent i0 + c is partial `wave`'s)
+            double x[COV_R], y[COV_R];
+            for (int a = 0; a < COV_R; a++) x[a] = sa[c * COV_T + lj + a], y[a] = sb[c * COV_T + lk + a];
+            for (int a = 0; a < COV_R; a++)
+                for (int b = 0; b < COV_R; b++) {
+                    const double prod = x[a] * y[b];
+                    acc[a][b] = acc[a][b] + prod;
+                }
+        }
+        __syncthreads();   // (the rows are read before the next pass, or the partial tiles, overwrite them)
+    }
+    for (int a = 0; a < COV_R; a++)
+        for (int b = 0; b < COV_R; b++) sbuf[(wave * COV_T + lj + a) * COV_T + lk + b] = acc[a][b];
+    __syncthreads();
+    for (int e = tid; e < COV_T * COV_T; e += COV_BS) {
+        const int j = tj * COV_T + e / COV_T, k = tk * COV_T + e % COV_T;
+        if (j > k || k >= nmom) continue;   // (below the diagonal of a diagonal tile, or the padding; j <= k < nmom)
+        double part[COV_P];
+        for (int t = 0; t < COV_P; t++) part[t] = sbuf[t * COV_T * COV_T + e];
+        for (int o = COV_P / 2; o > 0; o >>= 1)
+            for (int t = 0; t < o; t++) part[t] = part[t] + part[t + o];
+        cov[(size_t)j * nmom + k] = part[0];
+        cov[(size_t)k * nmom + j] = part[0];
+    }
+}
+
 // zero_first: the gateway's NaN fill starts at element 1 of its output array (egdst_simulator.c:105: element 0 is written by
 // agent 0 anyway, or stays 0.0); the batched estimation step (egdst_simulate_batch_moments) promises NaN moments for a draw
 // that failed or whose agent 0 has no value, so there every element is NaN

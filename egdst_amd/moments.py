@@ -6,6 +6,11 @@
     spec += [mo.median('M', periods=it) for it in range(nt)] + [mo.quantile('A', 0.9, where=('id', 1, 1))]
     means, counts, obj = solver.simulate_batch_spec(init, spec, target=t, W=W)
     data_means, data_counts = spec.evaluate(data_panel)      # the same definitions, summed in the same order, on the host
+    # the covariance of the moments (a spec without quantiles): per draw on the device, and of the data panel on the host, which
+    # is the Omega a user inverts into W
+    plain = mo.MomentSpec(spec[:-nt - 1], layout=solver.lib.info)
+    means, counts, cov = solver.simulate_batch_cov(init, plain)           # cov [ndraw, nmom, nmom]
+    data_means, data_counts, data_cov = plain.covariance(data_panel, parts=solver.lib.cov_parts)
 
 Columns are 0-based indices of the simulated panel (egdst_simulate, model.sims) or the tokens of the model strings:
 M C A V id ist mu sigma shock u df, then st1.. (nnst states), dc1.. (nnd decisions), eq1.. (neq equations).  `periods` is
@@ -292,6 +297,70 @@ class MomentSpec(list):
             counts[j] = n
             means[j] = p[0] / n if n else np.nan
         return means, counts
+
+    def covariance(self, sims, block=256, parts=4, layout=None):
+        """(means [nmom], counts [nmom], cov [nmom, nmom]) of a host panel sims [nsim, nt, nout]: the moments of
+        evaluate(sims, block) and their agent-clustered covariance Omega with the definitions and the summation order of
+        egdst_simulate_batch_spec_cov (include/egdst.h).  Agent i's score on record j is d_ij = (s_ij - m_j * c_ij) / N_j, with
+        c_ij the agent's qualifying pairs and s_ij the sum of their values in period order; Omega_jk = sum over i of
+        d_ij * d_ik: partial t < parts adds the rounded products of the agents i = t (mod parts) in ascending i, then the fixed
+        tree over the partials.  parts = the library's cov_parts (4) gives the device's bits.  The row and column of an empty
+        moment are NaN.  No degrees-of-freedom correction: nsim * cov estimates the asymptotic variance of the moment vector,
+        and cov of a data panel is what a user inverts into W.  Raises ValueError on a quantile, which has no covariance here."""
+        if parts < 1 or parts > 256 or parts & (parts - 1):
+            raise ValueError('MomentSpec.covariance: parts must be a power of two in [1, 256]')
+        means, counts, d = self.scores(sims, block=block, layout=layout)
+        nsim, nmom = d.shape
+        p = np.zeros((parts, nmom, nmom))
+        with np.errstate(invalid='ignore'):
+            for i0 in range(0, nsim, parts):   # one agent per partial and round: p_t = p_t + (d_ij * d_ik)
+                r = d[i0:i0 + parts]
+                p[:len(r)] += r[:, :, None] * r[:, None, :]
+            o = parts // 2
+            while o > 0:
+                p[:o] += p[o:2 * o]
+                o //= 2
+        cov = p[0]
+        upper = np.triu_indices(nmom, 1)
+        cov.T[upper] = cov[upper]   # (Omega_kj carries the bits of Omega_jk)
+        return means, counts, cov
+
+    def scores(self, sims, block=256, layout=None):
+        """(means [nmom], counts [nmom], d [nsim, nmom]): the moments of evaluate(sims, block) and every agent's score
+        d_ij = (s_ij - m_j * c_ij) / N_j as covariance documents it -- the agent's contribution to moment j, whose cross
+        products over the agents are Omega.  Elementwise IEEE operations: no summation order beyond an agent's own periods.
+        Raises ValueError on a quantile."""
+        sims = np.asarray(sims, dtype=np.float64)
+        if sims.ndim != 3:
+            raise ValueError('MomentSpec.scores: sims must be [nsim, nt, nout]')
+        rec = self.pack_lag(sims.shape[1], layout)
+        for j, q in enumerate(rec):
+            if q['kind'] == QUANTILE:
+                raise ValueError('MomentSpec: moment %d is a quantile, which has no covariance here' % j)
+        means, counts = self.evaluate(sims, block=block, layout=layout)
+        nsim = sims.shape[0]
+        d = np.empty((nsim, len(rec)))
+        for j, q in enumerate(rec):
+            f, l_ = int(q['it_first']), int(q['it_last']) + 1
+            v = sims[:, f:l_, q['col']]
+            ok = ~np.isnan(v)
+            with np.errstate(invalid='ignore'):
+                if q['cond_col'] >= 0:
+                    c = sims[:, f - int(q['cond_lag']):l_ - int(q['cond_lag']), q['cond_col']]
+                    ok &= (c >= q['cond_lo']) & (c <= q['cond_hi'])
+                if q['kind'] == CROSS:
+                    w = sims[:, f - int(q['lag2']):l_ - int(q['lag2']), q['col2']]
+                    ok &= ~np.isnan(w)
+                    x = v * w
+                elif q['kind'] == SHARE:
+                    x = ((v >= q['lo']) & (v <= q['hi'])).astype(np.float64)
+                else:
+                    x = v
+            # s_ij: from 0.0, the qualifying values in period order (adding +0.0 for the others leaves the sum unchanged)
+            s = np.cumsum(np.concatenate([np.zeros((nsim, 1)), np.where(ok, x, 0.0)], axis=1), axis=1)[:, -1]
+            with np.errstate(invalid='ignore', divide='ignore'):
+                d[:, j] = (s - means[j] * ok.sum(axis=1).astype(np.float64)) / np.float64(counts[j])
+        return means, counts, d
 
 
 def objective(means, counts, target, W):

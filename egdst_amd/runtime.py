@@ -35,7 +35,8 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_get_checksums', 'egdst_math_eval', 'egdst_get_evals_credited', 'egdst_simulate_batch_moments',
                'egdst_uniform', 'egdst_set_dbgout', 'egdst_get_dbgout', 'egdst_get_walk_stats',
                'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_group_profile',
-               'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys', 'egdst_simulate_batch_spec_lag']
+               'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys', 'egdst_simulate_batch_spec_lag',
+               'egdst_simulate_batch_spec_cov', 'egdst_cov_parts']
 
 
 class EgdstRuntimeError(RuntimeError):
@@ -90,6 +91,9 @@ class ModelLibrary:
                                                 C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         L.egdst_simulate_batch_spec_lag.argtypes = L.egdst_simulate_batch_spec.argtypes
+        L.egdst_simulate_batch_spec_cov.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_longlong, C.c_ulonglong,
+                                                    C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.egdst_cov_parts.argtypes = []
         L.egdst_uniform.restype = C.c_double
         L.egdst_uniform.argtypes = [C.c_ulonglong, C.c_ulonglong]
         L.egdst_set_dbgout.argtypes = [C.c_void_p, C.c_int]
@@ -151,6 +155,12 @@ class ModelLibrary:
     def quantile_lds_keys(self):
         """candidates up to which k_quantiles selects in LDS (the library's QNT_LDS_KEYS, egdst_quantile_lds_keys)"""
         return int(self.lib.egdst_quantile_lds_keys())
+
+    @property
+    def cov_parts(self):
+        """partial sums P of the covariance's summation order (the library's COV_P, egdst_cov_parts): what
+        MomentSpec.covariance takes as `parts` to give the device's bits"""
+        return int(self.lib.egdst_cov_parts())
 
     def quantile_eval(self, x, p):
         """(quantiles p of the host array x by the device's selection, the number of non-NaN values): egdst_quantile_eval,
@@ -581,6 +591,41 @@ class Solver:
                 raise EgdstRuntimeError(1, 'simulate_batch_spec: %s' % e) from None
         return self._estimation_step(entry, init, seed, rndtype, randstream_dev, nrand,
                                      (nmom,), (rec.ctypes.data_as(C.c_void_p), nmom), t, w, means_dev, counts_dev, obj_dev)
+
+    def simulate_batch_cov(self, init, spec, seed=0, rndtype=0, randstream_dev=None, nrand=0, means_dev=None, counts_dev=None,
+                           cov_dev=None):
+        """egdst_simulate_batch_spec_cov: the moments of simulate_batch_spec and, per draw, their covariance matrix Omega
+        (agent-clustered, include/egdst.h) -- spec is a moments.MomentSpec or an array of moments.MOMENT_DTYPE or
+        moments.MOMENT_LAG_DTYPE, promoted to lag records; a quantile is refused.  The *_dev arguments are device pointers
+        (ints); with none given, returns (means [ndraw, nmom], counts [ndraw, nmom], cov [ndraw, nmom, nmom]) through torch
+        tensors allocated here.  moments.MomentSpec.covariance(panel, parts=self.lib.cov_parts) is the same on the host."""
+        from . import moments
+        if isinstance(spec, moments.MomentSpec):
+            rec = spec.pack_lag(self.nt, layout=self.lib.info)
+        elif getattr(spec, 'dtype', None) == moments.MOMENT_LAG_DTYPE:
+            rec = np.ascontiguousarray(spec).reshape(-1)
+        else:
+            old = np.ascontiguousarray(spec, dtype=moments.MOMENT_DTYPE).reshape(-1)
+            rec = np.zeros(len(old), dtype=moments.MOMENT_LAG_DTYPE)   # (zero lags)
+            for f in moments.MOMENT_DTYPE.names:
+                rec[f] = old[f]
+        nmom = len(rec)
+        init = np.asfortranarray(np.atleast_2d(np.asarray(init, dtype=np.float64)))
+        own = means_dev is None and counts_dev is None and cov_dev is None
+        if own:
+            import torch
+            tm = torch.zeros(self.ndraw, nmom, dtype=torch.float64, device='cuda')
+            tc = torch.zeros(self.ndraw, nmom, dtype=torch.int32, device='cuda')
+            tv = torch.zeros(self.ndraw, nmom, nmom, dtype=torch.float64, device='cuda')
+            torch.cuda.current_stream().synchronize()   # (torch fills on its stream, the library writes on the handle's: _estimation_step)
+            means_dev, counts_dev, cov_dev = tm.data_ptr(), tc.data_ptr(), tv.data_ptr()
+        self.lib.check(self.lib.lib.egdst_simulate_batch_spec_cov(
+            self.h, _dp(init), init.shape[0], C.c_void_p(randstream_dev) if randstream_dev else None, int(nrand), int(seed),
+            int(rndtype), rec.ctypes.data_as(C.c_void_p), nmom, C.c_void_p(means_dev) if means_dev else None,
+            C.c_void_p(counts_dev) if counts_dev else None, C.c_void_p(cov_dev) if cov_dev else None))
+        if own:
+            return tm.cpu().numpy(), tc.cpu().numpy(), tv.cpu().numpy()
+        return None
 
     def call(self, sw, args, draw=0):
         """egdst_call gateway (egdst_call.c:17-164): sw 1 utility, 2 marginal utility, 3 discount, 4 budget, 5 marginal

@@ -263,6 +263,39 @@ int egdst_simulate_batch_spec_lag(egdst_handle *h, const double *init, int nsim,
                                   const double *target /* [nmom] */, const double *W /* [nmom x nmom] row-major */,
                                   double *means_dev /* [ndraw][nmom] */, int *counts_dev /* [ndraw][nmom] */,
                                   double *obj_dev /* [ndraw] */);
+/* The covariance of the simulated moments (new surface): the step of egdst_simulate_batch_spec_lag without an
+ * objective, and per draw the matrix Omega [nmom x nmom] of the moment vector.  Simulation, uniforms, rndtype, common random
+ * numbers, slicing and failed draws are those of egdst_simulate_batch_spec_lag, and means_dev / counts_dev (DEVICE, may be NULL)
+ * receive the bits that call writes.  cov_dev [ndraw][nmom][nmom] row-major is a DEVICE buffer and required.
+ * Meaning: Omega is the agent-clustered delta-method variance of the vector of ratio estimators m_j (each a sum over an agent's
+ * qualifying pairs divided by their number): the agents are the independent units, and all periods of an agent enter as one
+ * cluster.  No degrees-of-freedom correction; nsim * Omega estimates the asymptotic variance.  For one period without a
+ * condition Omega_jj is the population variance of the values divided by N_j; for a moment pooled over periods it is not
+ * divided by the number of periods again.  It gives the efficient weighting matrix (its inverse, or a generalised inverse:
+ * shares that sum to one make it singular), standard errors and the simulation-noise term of the sandwich formula.
+ * For one draw, records j and k (kinds 0, 1 and 2) and agent i, every operation a rounded fp64 operation, no FMA:
+ *   c_ij   the number of the agent's qualifying pairs (those egdst_moment_lag's checks accept in the record's period range);
+ *   s_ij   starts at 0.0 and adds the agent's qualifying values in ascending period (kind 2 adds 1.0 or 0.0);
+ *   N_j    = sum over i of c_ij, the count of the moment; m_j its mean, the bits egdst_simulate_batch_spec_lag writes;
+ *   d_ij   = (s_ij - m_j * (double)c_ij) / (double)N_j       the agent's score: one product, one difference, one quotient;
+ *   Omega_jk = sum over i of d_ij * d_ik in this order, P = egdst_cov_parts() = 4 in this library:
+ *            partial t (0 <= t < P) starts at 0.0 and, for the agents i = t (mod P) in ascending i, p_t = p_t + (d_ij * d_ik),
+ *            the product rounded, then the sum; then for o = P/2 .. 1: p[t] += p[t+o] (t < o); Omega_jk = p[0].
+ *   Omega_kj carries the bits of Omega_jk.
+ * An empty moment (N_j = 0) has m_j = NaN and d_ij = NaN: row and column j of Omega are NaN (the payload is not part of the
+ * contract).  A draw that failed to solve has counts 0, NaN means and an all-NaN Omega.
+ * EGDST_E_ARG before anything is launched, with the moment's index in egdst_last_error where a record is at fault: everything
+ * egdst_simulate_batch_spec_lag refuses; a kind-3 record (a quantile has no covariance here: its influence function needs a
+ * density estimate); cov_dev == NULL. */
+int egdst_simulate_batch_spec_cov(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
+                                  long long nrand, unsigned long long seed, int rndtype,
+                                  const egdst_moment_lag *spec, int nmom,
+                                  double *means_dev /* [ndraw][nmom], may be NULL */,
+                                  int *counts_dev   /* [ndraw][nmom], may be NULL */,
+                                  double *cov_dev   /* [ndraw][nmom][nmom] row-major, required */);
+/* The number P of partial sums of the covariance's summation order (build constant COV_P: one per wave of k_moment_cov's
+ * 256-thread workgroup), a power of two in [1, 256]. */
+int egdst_cov_parts(void);
 /* Uniform number k of stream `seed` (host replay of the device generator): with z = seed + (k+1)*0x9E3779B97F4A7C15,
  * z = (z ^ z>>30)*0xBF58476D1CE4E5B9, z = (z ^ z>>27)*0x94D049BB133111EB, z ^= z>>31 (splitmix64): (z >> 11) * 2^-53. */
 double egdst_uniform(unsigned long long seed, unsigned long long k);
