@@ -981,11 +981,17 @@ static int enqueue_solve(egdst_handle *h)
 #endif
     h->solve_seq++;
     {   // the Batch every group's kernels read (constant address space), one copy per group with its schedule range
+        // The staging entries are pinned, and the upload of an earlier solve that is still queued reads them when it runs:
+        // solves may be enqueued back to back, so every field is stored once with its final value.  Between two such
+        // solves only sorted_valid differs (the schedule changes in egdst_sync alone); a queued solve that picks up a
+        // later solve's stamp uses it in all of its kernels, and a stamp left by an earlier solve reads as "out of
+        // order", the general search.
         for (int gi = 0; gi < G; gi++) {
-            h->b_host[gi] = b;
-            h->b_host[gi].draw0 = (G > 1) ? h->gstart[gi] : 0;
-            h->b_host[gi].gdraws = ((G > 1) ? h->gstart[gi + 1] : g.ndraw) - h->b_host[gi].draw0;
-            h->b_host[gi].sorted_valid = p.sortcheck ? (int)((h->solve_seq & 0x3ffffu) << 12) + 1 : 0;
+            Batch e = b;
+            e.draw0 = (G > 1) ? h->gstart[gi] : 0;
+            e.gdraws = ((G > 1) ? h->gstart[gi + 1] : g.ndraw) - e.draw0;
+            e.sorted_valid = p.sortcheck ? (int)((h->solve_seq & 0x3ffffu) << 12) + 1 : 0;
+            h->b_host[gi] = e;
         }
         HIPCHK(hipMemcpyAsync(h->b_dev, h->b_host, sizeof(Batch) * G, hipMemcpyHostToDevice, s));
     }

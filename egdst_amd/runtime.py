@@ -293,6 +293,14 @@ class Solver:
         self.lib.check(self.lib.lib.egdst_geometry(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def device_tables(self, it):
+        """(M, C, V, len, stride) of period `it` where the handle keeps it: device pointers (ints) of the M, C and V tables,
+        [ndraw][nst][stride] doubles, and of the lengths, [ndraw][nst] ints (egdst_device_tables), with the row stride of
+        egdst_geometry.  Without history a period lives in slot it & 1: after a solve the two slots hold periods 0 and 1."""
+        p = [C.c_void_p() for _ in range(4)]
+        self.lib.check(self.lib.lib.egdst_device_tables(self.h, int(it), *[C.byref(x) for x in p]))
+        return tuple(int(x.value or 0) for x in p) + (self.geometry()[1],)
+
     def _route(self, draw):
         """(solver, local draw) that holds the results of `draw`"""
         if len(self._redo):

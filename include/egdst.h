@@ -134,7 +134,9 @@ int egdst_set_params_dev(egdst_handle *h, const double *params_dev, int ndraw);
 int egdst_get_params(egdst_handle *h, double *params /* host, [ndraw*nparam] */);
 
 /* Backward induction for all draws (egdst_solver.c:258-339).  _async only enqueues on the handle's
- * stream; egdst_sync waits and returns the first non-zero per-draw status (or 0). */
+ * stream; egdst_sync waits and returns the first non-zero per-draw status (or 0).  Solves may be enqueued back to
+ * back without a host synchronisation in between (egdst_set_params_dev, egdst_solve_async, egdst_objective_dev, again):
+ * each follows the one before on the handle's stream. */
 int egdst_solve_async(egdst_handle *h);
 int egdst_sync(egdst_handle *h);
 int egdst_solve(egdst_handle *h);

@@ -45,7 +45,8 @@ def _c2_case():
 @pytest.mark.parametrize('rndtype', [0, 1])
 def test_per_period_spec_is_the_batch_moments_path(rndtype):
     """C2 setup of test_estimation_step_on_device: means, counts and the objective with a diagonal W bit-identical to
-    simulate_batch_moments; the failing draws give NaN / 0 / NaN.  The two are doors of one kernel, so simulate_batch_moments is
+    simulate_batch_moments; a failing draw would give NaN / 0 / NaN, but at ngridm=300 none of these fails (draws that do:
+    tests/test_gpu_estimation_loop.py::test_estimation_step_with_draws_that_fail).  The two are doors of one kernel, so simulate_batch_moments is
     pinned by itself as well: for every draw (the oracle solves all eight) bit-identical to the per-period spec evaluated in
     the device's order on the oracle's paths for the host replay of the uniforms, and to moments.objective with the weights as
     a diagonal; 420 cells, so the objective kernel crosses a boundary of its 256-row chunks."""
