@@ -128,6 +128,53 @@ def quantile_rank(p, n):
     return min(max(int(math.ceil(float(p) * float(n))), 1), int(n))
 
 
+def convert_records(rec, dtype):
+    """rec, an array of MOMENT_DTYPE or MOMENT_LAG_DTYPE, as a contiguous [nmom] array of `dtype` (one of the two): an
+    egdst_moment widens with zero lags, an egdst_moment_lag narrows once its lags are seen to be zero (ValueError if not)"""
+    src = MOMENT_LAG_DTYPE if getattr(rec, 'dtype', None) == MOMENT_LAG_DTYPE else MOMENT_DTYPE
+    rec = np.ascontiguousarray(rec, dtype=src).reshape(-1)
+    if src == dtype:
+        return rec
+    if dtype == MOMENT_DTYPE and (rec['lag2'].any() or rec['cond_lag'].any()):
+        raise ValueError('a moment has a lag, which egdst_moment cannot carry')
+    out = np.zeros(len(rec), dtype=dtype)   # (zero lags)
+    for f in MOMENT_DTYPE.names:
+        out[f] = rec[f]
+    return out
+
+
+def lag_records(spec, nt, layout=None):
+    """(rec, lag): what a caller may pass as moments -- a MomentSpec, an array of MOMENT_DTYPE or one of MOMENT_LAG_DTYPE -- as
+    an [nmom] array of MOMENT_LAG_DTYPE, and whether it needs the entry that takes those (egdst_simulate_batch_spec_lag): a
+    MomentSpec with a lag or an array of MOMENT_LAG_DTYPE does, and then rec goes as it is; otherwise
+    convert_records(rec, MOMENT_DTYPE) is what egdst_simulate_batch_spec takes."""
+    if isinstance(spec, MomentSpec):
+        return spec.pack_lag(nt, layout), spec.lagged
+    return convert_records(spec, MOMENT_LAG_DTYPE), getattr(spec, 'dtype', None) == MOMENT_LAG_DTYPE
+
+
+def _moment_term(sims, q):
+    """(ok, x), both [nsim, periods of q]: the host's eg_moment_term -- which (agent, period) pairs of the panel qualify for
+    the packed MOMENT_LAG_DTYPE record q, and with which value: v, v * w, or the share's 1.0 / 0.0 (a quantile: v).  The
+    condition is read cond_lag periods away, the second factor lag2 periods away, and each must be present there."""
+    f, l_ = int(q['it_first']), int(q['it_last']) + 1
+    v = sims[:, f:l_, q['col']]
+    ok = ~np.isnan(v)
+    with np.errstate(invalid='ignore'):
+        if q['cond_col'] >= 0:
+            c = sims[:, f - int(q['cond_lag']):l_ - int(q['cond_lag']), q['cond_col']]   # (pack_lag: inside the panel)
+            ok &= (c >= q['cond_lo']) & (c <= q['cond_hi'])
+        if q['kind'] == CROSS:
+            w = sims[:, f - int(q['lag2']):l_ - int(q['lag2']), q['col2']]
+            ok &= ~np.isnan(w)
+            x = v * w
+        elif q['kind'] == SHARE:
+            x = ((v >= q['lo']) & (v <= q['hi'])).astype(np.float64)
+        else:
+            x = v
+    return ok, x
+
+
 class MomentSpec(list):
     """A list of Moment records, resolved against a model's column layout (`layout`: the library's model info, a Solver, a
     ModelLibrary, a model, or (nnst, nnd, neq)).  pack(nt) gives the egdst_moment array, pack_lag(nt) the egdst_moment_lag array (a
@@ -176,11 +223,7 @@ class MomentSpec(list):
         lag: that one packs with pack_lag"""
         if self.lagged:
             raise ValueError('MomentSpec: a moment has a lag, which egdst_moment cannot carry: use pack_lag')
-        rec = self.pack_lag(nt, layout)
-        out = np.zeros(len(rec), dtype=MOMENT_DTYPE)
-        for f in MOMENT_DTYPE.names:
-            out[f] = rec[f]
-        return out
+        return convert_records(self.pack_lag(nt, layout), MOMENT_DTYPE)
 
     def pack_lag(self, nt, layout=None):
         """[nmom] array of MOMENT_LAG_DTYPE, with or without lags; raises ValueError on a bad name, kind, column, lag or
@@ -257,37 +300,21 @@ class MomentSpec(list):
         means = np.empty(len(rec))
         counts = np.empty(len(rec), dtype=np.int64)
         for j, q in enumerate(rec):
-            f, l_ = int(q['it_first']), int(q['it_last']) + 1
-            v = sims[:, f:l_, q['col']]
-            ok = ~np.isnan(v)
-            if q['cond_col'] >= 0:
-                c = sims[:, f - int(q['cond_lag']):l_ - int(q['cond_lag']), q['cond_col']]   # (pack_lag: inside the panel)
-                with np.errstate(invalid='ignore'):
-                    ok &= (c >= q['cond_lo']) & (c <= q['cond_hi'])
+            ok, x = _moment_term(sims, q)
             if q['kind'] == QUANTILE:
                 n = int(ok.sum())
                 counts[j] = n
                 means[j] = np.nan
                 if n:
-                    key = np.sort(quantile_keys(v[ok]))[quantile_rank(q['lo'], n) - 1]
+                    key = np.sort(quantile_keys(x[ok]))[quantile_rank(q['lo'], n) - 1]
                     u = key & np.uint64((1 << 63) - 1) if key >> np.uint64(63) else ~key
                     means[j] = np.array([u], dtype=np.uint64).view(np.float64)[0]
                 continue
-            if q['kind'] == CROSS:
-                w = sims[:, f - int(q['lag2']):l_ - int(q['lag2']), q['col2']]
-                ok &= ~np.isnan(w)
-                with np.errstate(invalid='ignore'):
-                    x = v * w
-            elif q['kind'] == SHARE:
-                with np.errstate(invalid='ignore'):
-                    x = ((v >= q['lo']) & (v <= q['hi'])).astype(np.float64)
-            else:
-                x = v
             x = np.where(ok, x, 0.0)   # (adding +0.0 leaves a partial unchanged: it starts at +0.0 and never becomes -0.0)
             # partial t adds agents t, t+block, ... in order, each agent's periods in order: [block, nb * periods] rows
-            xp = np.zeros((nb * block, l_ - f))
+            xp = np.zeros((nb * block, x.shape[1]))
             xp[:nsim] = x
-            rows = xp.reshape(nb, block, l_ - f).transpose(1, 0, 2).reshape(block, -1)
+            rows = xp.reshape(nb, block, x.shape[1]).transpose(1, 0, 2).reshape(block, -1)
             p = np.cumsum(rows, axis=1)[:, -1].copy() if rows.shape[1] else np.zeros(block)
             n = ok.sum()
             o = block // 2
@@ -341,21 +368,7 @@ class MomentSpec(list):
         nsim = sims.shape[0]
         d = np.empty((nsim, len(rec)))
         for j, q in enumerate(rec):
-            f, l_ = int(q['it_first']), int(q['it_last']) + 1
-            v = sims[:, f:l_, q['col']]
-            ok = ~np.isnan(v)
-            with np.errstate(invalid='ignore'):
-                if q['cond_col'] >= 0:
-                    c = sims[:, f - int(q['cond_lag']):l_ - int(q['cond_lag']), q['cond_col']]
-                    ok &= (c >= q['cond_lo']) & (c <= q['cond_hi'])
-                if q['kind'] == CROSS:
-                    w = sims[:, f - int(q['lag2']):l_ - int(q['lag2']), q['col2']]
-                    ok &= ~np.isnan(w)
-                    x = v * w
-                elif q['kind'] == SHARE:
-                    x = ((v >= q['lo']) & (v <= q['hi'])).astype(np.float64)
-                else:
-                    x = v
+            ok, x = _moment_term(sims, q)
             # s_ij: from 0.0, the qualifying values in period order (adding +0.0 for the others leaves the sum unchanged)
             s = np.cumsum(np.concatenate([np.zeros((nsim, 1)), np.where(ok, x, 0.0)], axis=1), axis=1)[:, -1]
             with np.errstate(invalid='ignore', divide='ignore'):

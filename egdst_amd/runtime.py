@@ -530,30 +530,30 @@ class Solver:
                                                            _dp(means), _ip(counts)))
         return means, counts
 
-    def _estimation_step(self, entry, init, seed, rndtype, randstream_dev, nrand, shape, spec_args, t, w, means_dev, counts_dev,
-                         obj_dev):
-        """What simulate_batch_moments and simulate_batch_spec share: `entry` is the library's function, spec_args what it
-        takes between rndtype and the target, shape the moments of a draw, t / w the host target and weights (None: no
-        objective).  With no device pointers given the results go through torch tensors allocated here and are returned."""
+    def _estimation_step(self, entry, init, seed, rndtype, randstream_dev, nrand, shape, args, third, means_dev, counts_dev,
+                         third_dev):
+        """The one call path of simulate_batch_moments, simulate_batch_spec and simulate_batch_cov: `entry` is the library's
+        function, args what it takes between rndtype and the outputs (records, target, weights), shape the moments of a
+        draw, third the shape per draw of the third output -- () the objective, (nmom, nmom) the covariance, None: there is
+        none.  With no device pointers given the results go through torch tensors allocated here and are returned."""
         init = np.asfortranarray(np.atleast_2d(np.asarray(init, dtype=np.float64)))
-        own = means_dev is None and counts_dev is None and obj_dev is None
+        own = means_dev is None and counts_dev is None and third_dev is None
         if own:
             import torch
             tm = torch.zeros(self.ndraw, *shape, dtype=torch.float64, device='cuda')
             tc = torch.zeros(self.ndraw, *shape, dtype=torch.int32, device='cuda')
-            to = torch.zeros(self.ndraw, dtype=torch.float64, device='cuda') if w is not None else None
+            t3 = torch.zeros(self.ndraw, *third, dtype=torch.float64, device='cuda') if third is not None else None
             # torch fills them on ITS stream; the library writes them on the handle's: without this the fill may land after the
             # results (seen once in a few hundred runs: all moments and objectives zero)
             torch.cuda.current_stream().synchronize()
             means_dev, counts_dev = tm.data_ptr(), tc.data_ptr()
-            obj_dev = to.data_ptr() if to is not None else None
+            third_dev = t3.data_ptr() if t3 is not None else None
         self.lib.check(entry(
             self.h, _dp(init), init.shape[0], C.c_void_p(randstream_dev) if randstream_dev else None, int(nrand), int(seed),
-            int(rndtype), *spec_args, _dp(t) if t is not None else None, _dp(w) if w is not None else None,
-            C.c_void_p(means_dev) if means_dev else None, C.c_void_p(counts_dev) if counts_dev else None,
-            C.c_void_p(obj_dev) if obj_dev else None))
+            int(rndtype), *args, C.c_void_p(means_dev) if means_dev else None, C.c_void_p(counts_dev) if counts_dev else None,
+            C.c_void_p(third_dev) if third_dev else None))
         if own:
-            return tm.cpu().numpy(), tc.cpu().numpy(), to.cpu().numpy() if to is not None else None
+            return tm.cpu().numpy(), tc.cpu().numpy(), t3.cpu().numpy() if t3 is not None else None
         return None
 
     def simulate_batch_moments(self, init, seed=0, rndtype=0, target=None, weight=None, randstream_dev=None, nrand=0,
@@ -565,7 +565,7 @@ class Solver:
         t = np.ascontiguousarray(np.zeros(ncell) if target is None else target, dtype=np.float64).reshape(-1)
         w = np.ascontiguousarray(np.zeros(ncell) if weight is None else weight, dtype=np.float64).reshape(-1)
         return self._estimation_step(self.lib.lib.egdst_simulate_batch_moments, init, seed, rndtype, randstream_dev, nrand,
-                                     (self.nt, self.lib.nout), (), t, w, means_dev, counts_dev, obj_dev)
+                                     (self.nt, self.lib.nout), (_dp(t), _dp(w)), (), means_dev, counts_dev, obj_dev)
 
     def simulate_batch_spec(self, init, spec, seed=0, rndtype=0, target=None, W=None, randstream_dev=None, nrand=0,
                             means_dev=None, counts_dev=None, obj_dev=None):
@@ -576,15 +576,10 @@ class Solver:
         The *_dev arguments are device pointers (ints); with none given, returns (means [ndraw, nmom], counts [ndraw, nmom],
         objective [ndraw] or None) through torch tensors allocated here."""
         from . import moments
-        entry = self.lib.lib.egdst_simulate_batch_spec
-        if isinstance(spec, moments.MomentSpec) and spec.lagged:
-            rec, entry = spec.pack_lag(self.nt, layout=self.lib.info), self.lib.lib.egdst_simulate_batch_spec_lag
-        elif isinstance(spec, moments.MomentSpec):
-            rec = spec.pack(self.nt, layout=self.lib.info)
-        elif getattr(spec, 'dtype', None) == moments.MOMENT_LAG_DTYPE:
-            rec, entry = np.ascontiguousarray(spec).reshape(-1), self.lib.lib.egdst_simulate_batch_spec_lag
-        else:
-            rec = np.ascontiguousarray(spec, dtype=moments.MOMENT_DTYPE).reshape(-1)
+        rec, lag = moments.lag_records(spec, self.nt, layout=self.lib.info)
+        entry = self.lib.lib.egdst_simulate_batch_spec_lag
+        if not lag:
+            rec, entry = moments.convert_records(rec, moments.MOMENT_DTYPE), self.lib.lib.egdst_simulate_batch_spec
         nmom = len(rec)
         if (target is None) != (W is None):
             raise EgdstRuntimeError(1, 'simulate_batch_spec: the objective needs both target and W')
@@ -597,8 +592,9 @@ class Solver:
                 w = moments.weight_matrix(W, nmom)
             except ValueError as e:
                 raise EgdstRuntimeError(1, 'simulate_batch_spec: %s' % e) from None
-        return self._estimation_step(entry, init, seed, rndtype, randstream_dev, nrand,
-                                     (nmom,), (rec.ctypes.data_as(C.c_void_p), nmom), t, w, means_dev, counts_dev, obj_dev)
+        return self._estimation_step(entry, init, seed, rndtype, randstream_dev, nrand, (nmom,),
+                                     (rec.ctypes.data_as(C.c_void_p), nmom, _dp(t) if t is not None else None,
+                                      _dp(w) if w is not None else None), () if w is not None else None, means_dev, counts_dev, obj_dev)
 
     def simulate_batch_cov(self, init, spec, seed=0, rndtype=0, randstream_dev=None, nrand=0, means_dev=None, counts_dev=None,
                            cov_dev=None):
@@ -608,32 +604,10 @@ class Solver:
         (ints); with none given, returns (means [ndraw, nmom], counts [ndraw, nmom], cov [ndraw, nmom, nmom]) through torch
         tensors allocated here.  moments.MomentSpec.covariance(panel, parts=self.lib.cov_parts) is the same on the host."""
         from . import moments
-        if isinstance(spec, moments.MomentSpec):
-            rec = spec.pack_lag(self.nt, layout=self.lib.info)
-        elif getattr(spec, 'dtype', None) == moments.MOMENT_LAG_DTYPE:
-            rec = np.ascontiguousarray(spec).reshape(-1)
-        else:
-            old = np.ascontiguousarray(spec, dtype=moments.MOMENT_DTYPE).reshape(-1)
-            rec = np.zeros(len(old), dtype=moments.MOMENT_LAG_DTYPE)   # (zero lags)
-            for f in moments.MOMENT_DTYPE.names:
-                rec[f] = old[f]
+        rec, _ = moments.lag_records(spec, self.nt, layout=self.lib.info)
         nmom = len(rec)
-        init = np.asfortranarray(np.atleast_2d(np.asarray(init, dtype=np.float64)))
-        own = means_dev is None and counts_dev is None and cov_dev is None
-        if own:
-            import torch
-            tm = torch.zeros(self.ndraw, nmom, dtype=torch.float64, device='cuda')
-            tc = torch.zeros(self.ndraw, nmom, dtype=torch.int32, device='cuda')
-            tv = torch.zeros(self.ndraw, nmom, nmom, dtype=torch.float64, device='cuda')
-            torch.cuda.current_stream().synchronize()   # (torch fills on its stream, the library writes on the handle's: _estimation_step)
-            means_dev, counts_dev, cov_dev = tm.data_ptr(), tc.data_ptr(), tv.data_ptr()
-        self.lib.check(self.lib.lib.egdst_simulate_batch_spec_cov(
-            self.h, _dp(init), init.shape[0], C.c_void_p(randstream_dev) if randstream_dev else None, int(nrand), int(seed),
-            int(rndtype), rec.ctypes.data_as(C.c_void_p), nmom, C.c_void_p(means_dev) if means_dev else None,
-            C.c_void_p(counts_dev) if counts_dev else None, C.c_void_p(cov_dev) if cov_dev else None))
-        if own:
-            return tm.cpu().numpy(), tc.cpu().numpy(), tv.cpu().numpy()
-        return None
+        return self._estimation_step(self.lib.lib.egdst_simulate_batch_spec_cov, init, seed, rndtype, randstream_dev, nrand, (nmom,),
+                                     (rec.ctypes.data_as(C.c_void_p), nmom), (nmom, nmom), means_dev, counts_dev, cov_dev)
 
     def call(self, sw, args, draw=0):
         """egdst_call gateway (egdst_call.c:17-164): sw 1 utility, 2 marginal utility, 3 discount, 4 budget, 5 marginal

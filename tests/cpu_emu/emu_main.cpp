@@ -3,23 +3,20 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "../../include/egdst.h"
+#include "emu_case.h"
 int main(int argc, char **argv)
 {
     if (argc < 2) return 2;
     FILE *f = fopen(argv[1], "r");
     if (!f) return 2;
-    egdst_desc d;
-    int np;
-    if (fscanf(f, "%d %d %d %d %d %d %lf %lf %d", &d.t0, &d.T, &d.ngridm, &d.ngridmax, &d.nthrhmax, &d.ny, &d.mmax, &d.a0, &np) != 9) return 2;
-    std::vector<double> q(2 * d.ny), par(np > 0 ? np : 1);
-    for (auto &x : q) if (fscanf(f, "%lf", &x) != 1) return 2;
-    for (int i = 0; i < np; i++) if (fscanf(f, "%lf", &par[i]) != 1) return 2;
-    d.quadrature = q.data();
+    emu_case c;
+    const bool read = emu_read_solver_case(f, c);
+    fclose(f);
+    if (!read) return 2;
     egdst_handle *h = nullptr;
-    int rc = egdst_create(&d, 1, 1, nullptr, &h);
+    int rc = egdst_create(&c.d, 1, 1, nullptr, &h);
     if (rc) { printf("create rc=%d %s\n", rc, egdst_last_error()); return 1; }
-    egdst_set_params(h, par.data(), 1);
+    egdst_set_params(h, c.par.data(), 1);
     rc = egdst_solve(h);
     long long ev = 0;
     egdst_get_evals(h, &ev, nullptr);

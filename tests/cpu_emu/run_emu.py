@@ -7,18 +7,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 sys.path.insert(0, os.path.join(ROOT, 'tests', 'cpu_emu'))
 import build_emu  # noqa: E402
-from egdst_amd import build, codegen, runtime  # noqa: E402
+from egdst_amd import runtime  # noqa: E402
+from estimation_emu import write_modelspec  # noqa: E402
 from oracle_harness import Oracle  # noqa: E402
 from parity import compare  # noqa: E402
 
 
 def run(model, sanitize=True, env_bs=1, parallel_blocks=False, wave=1):
-    text = codegen.generate_modelspec(model)
-    d = os.path.join(build.MODELS_DIR, build.model_tag(model, text))
-    os.makedirs(d, exist_ok=True)
-    spec = os.path.join(d, 'modelspec.h')
-    if not os.path.exists(spec) or open(spec).read() != text:
-        open(spec, 'w').write(text)
+    d = write_modelspec(model)
     lib = runtime.ModelLibrary(build_emu.build(d, sanitize, env_bs, parallel_blocks, wave))
     s = runtime.Solver(lib, model.descriptor(), ndraw=1, keep_history=True, rows_cap=int(os.environ.get('EMU_ROWS_CAP', '0')))
     s.set_params(model.param_vector())

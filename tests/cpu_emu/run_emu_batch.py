@@ -5,16 +5,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests', 'cpu_emu'))
 import numpy as np
 import build_emu
-from egdst_amd import build, codegen, runtime, workloads
+from egdst_amd import runtime, workloads
+from estimation_emu import write_modelspec
 from oracle_harness import Oracle
 from parity import compare
 
 
 def run(model, P, keep_history, sanitize='address', env_bs=1, wave=1):
-    text = codegen.generate_modelspec(model)
-    d = os.path.join(build.MODELS_DIR, build.model_tag(model, text))
-    os.makedirs(d, exist_ok=True)
-    open(os.path.join(d, 'modelspec.h'), 'w').write(text)
+    d = write_modelspec(model)
     lib = runtime.ModelLibrary(build_emu.build(d, sanitize, env_bs, False, wave))
     s = runtime.Solver(lib, model.descriptor(), ndraw=len(P), keep_history=keep_history, rows_cap=int(os.environ.get('EMU_ROWS_CAP', '0')))
     s.set_params(P)

@@ -5,17 +5,15 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests', 'cpu_emu'))
 import build_emu
-from egdst_amd import build, codegen, runtime, workloads
+from egdst_amd import runtime, workloads
+from estimation_emu import write_modelspec
 from oracle_harness import Oracle
 from parity import compare
 
 if __name__ == '__main__':
     m, gen = workloads.c2(a0=0)
     P = gen(4096)
-    text = codegen.generate_modelspec(m)
-    d = os.path.join(build.MODELS_DIR, build.model_tag(m, text))
-    os.makedirs(d, exist_ok=True)
-    open(os.path.join(d, 'modelspec.h'), 'w').write(text)
+    d = write_modelspec(m)
     san = os.environ.get('EMU_SANITIZE', '0')
     lib = runtime.ModelLibrary(build_emu.build(d, {'0': False}.get(san, san), int(os.environ.get('EMU_ENV_BS', '1')), False, int(os.environ.get('EMU_WAVE', '1'))))
     orc = Oracle(m)

@@ -5,17 +5,15 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests', 'cpu_emu'))
 import build_emu
-from egdst_amd import build, codegen, runtime, workloads
+from egdst_amd import runtime, workloads
+from estimation_emu import write_modelspec
 from oracle_harness import Oracle
 
 if __name__ == '__main__':
     m, gen = workloads.c2(a0=0)
     P = gen(1024)
     idx = [int(a) for a in sys.argv[1:]]
-    text = codegen.generate_modelspec(m)
-    d = os.path.join(build.MODELS_DIR, build.model_tag(m, text))
-    os.makedirs(d, exist_ok=True)
-    open(os.path.join(d, 'modelspec.h'), 'w').write(text)
+    d = write_modelspec(m)
     lib = runtime.ModelLibrary(build_emu.build(d, False, 1, False, 1))
     orc = Oracle(m)
     for kh in (True, False):

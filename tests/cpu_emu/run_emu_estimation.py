@@ -7,16 +7,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests', 'cpu_emu'))
 import numpy as np
 import build_emu
-from egdst_amd import build, codegen, runtime, workloads
+from egdst_amd import runtime, workloads
+from estimation_emu import write_modelspec
 from egdst_amd import moments as mo
 from oracle_harness import Oracle
 import estimation_case
-
-
-def bits_equal(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
+from estimation_case import bits_equal
 
 
 def check_bits(s, orc, P, init, seed, rndtype):
@@ -58,10 +54,7 @@ if __name__ == '__main__':
     san = os.environ.get('EMU_SANITIZE', 'address')
     m, gen = workloads.c2(a0=0, ngridm=60, T=10, ny=5)
     P = gen(5)
-    text = codegen.generate_modelspec(m)
-    d = os.path.join(build.MODELS_DIR, build.model_tag(m, text))
-    os.makedirs(d, exist_ok=True)
-    open(os.path.join(d, 'modelspec.h'), 'w').write(text)
+    d = write_modelspec(m)
     lib = runtime.ModelLibrary(build_emu.build(d, {'0': False}.get(san, san), 1, False, 1))
     s = runtime.Solver(lib, m.descriptor(), ndraw=len(P), keep_history=True)
     s.set_params(P)

@@ -10,7 +10,7 @@ import numpy as np
 import build_emu
 from egdst_amd import examples, runtime, workloads
 import estimation_loop_case as lc
-from run_emu_moment_cov import write_modelspec
+from estimation_emu import write_modelspec
 
 
 def perturbed(m, n, seed=21):

@@ -9,7 +9,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests', 'cpu_emu'))
 import numpy as np
 import build_emu
-from egdst_amd import build, codegen, runtime, workloads
+from egdst_amd import runtime, workloads
+from estimation_emu import write_modelspec
 from oracle_harness import Oracle
 from parity import compare
 
@@ -28,21 +29,13 @@ if __name__ == '__main__':
     d0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     m, gen = workloads.c2(a0=-5.0, ngridm=int(os.environ.get("EMU_NGRIDM", 300)), T=int(os.environ.get("EMU_T", 20)), ny=10)
     P = gen(d0 + nd)[d0:]
-    text = codegen.generate_modelspec(m)
-    d = os.path.join(build.MODELS_DIR, build.model_tag(m, text))
-    os.makedirs(d, exist_ok=True)
-    open(os.path.join(d, 'modelspec.h'), 'w').write(text)
+    d = write_modelspec(m)
     san = os.environ.get('EMU_SANITIZE', '0')
     san = {'0': False}.get(san, san)
     res = {}
     for flag in ('', '-DEG_FIX_REUSE=0'):
-        # (a directory per variant: build_emu.build returns the default library of a directory whenever that one is current)
-        dv = d + ('_' + ''.join(c if c.isalnum() else '_' for c in flag) if flag else '')
-        os.makedirs(dv, exist_ok=True)
-        if dv != d:
-            open(os.path.join(dv, 'modelspec.h'), 'w').write(text)
-        os.environ['EMU_EXTRA_FLAGS'] = flag
-        res[flag] = solve(runtime.ModelLibrary(build_emu.build(dv, san, 1, False, 1)), m, P)
+        os.environ['EMU_EXTRA_FLAGS'] = flag   # (build_emu.build names the library after its flags)
+        res[flag] = solve(runtime.ModelLibrary(build_emu.build(d, san, 1, False, 1)), m, P)
     os.environ.pop('EMU_EXTRA_FLAGS')
     (sa, st_a, ev_a, rg_a), (sb, st_b, ev_b, rg_b) = res[''], res['-DEG_FIX_REUSE=0']
     orc = Oracle(m)

@@ -8,16 +8,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests', 'cpu_emu'))
 import numpy as np
 import build_emu
-from egdst_amd import build, codegen, examples, runtime
+from egdst_amd import examples, runtime
+from estimation_emu import full_w, write_modelspec
 from egdst_amd import moments as mo
 from oracle_harness import Oracle
 import estimation_case
-
-
-def bits_equal(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
+from estimation_case import bits_equal
 
 
 def occ3_spec(nt, layout):
@@ -30,18 +26,10 @@ def occ3_spec(nt, layout):
     return mo.MomentSpec(items, layout=layout)
 
 
-def full_w(n, seed=11):
-    a = np.random.default_rng(seed).normal(size=(n, n))
-    return (a @ a.T) / n
-
-
 if __name__ == '__main__':
     san = os.environ.get('EMU_SANITIZE', 'address')
     m = examples.occ3(T=6, ngridm=30, ngridmax=100)
-    text = codegen.generate_modelspec(m)
-    d = os.path.join(build.MODELS_DIR, build.model_tag(m, text))
-    os.makedirs(d, exist_ok=True)
-    open(os.path.join(d, 'modelspec.h'), 'w').write(text)
+    d = write_modelspec(m)
     lib = runtime.ModelLibrary(build_emu.build(d, {'0': False}.get(san, san), 1, False, 1))
     rng = np.random.default_rng(4)
     P = m.param_vector()[None] * (1 + 0.15 * rng.uniform(-1, 1, (4, len(m.param_vector()))))

@@ -2,24 +2,11 @@
 pooled, next to the other kinds -- against MomentSpec.evaluate(block=1) on the oracle's paths for the host replay of the
 uniforms.  EMU_EXTRA_FLAGS chooses what the build exercises: -DQNT_LDS_KEYS=64 puts the 48 agents of a period into LDS and the
 pooled records into the global regime; -DEG_SIM_SLICE_BYTES=... makes the draws take several slices of paths."""
-import os
-import re
-import sys
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests', 'cpu_emu'))
 import numpy as np
-import build_emu
-from egdst_amd import build, codegen, examples, runtime
+import estimation_emu as emu
+from estimation_emu import NSIM, NDRAW, flag, full_w
 from egdst_amd import moments as mo
-from oracle_harness import Oracle
-import estimation_case
-from run_emu_moment_spec import bits_equal, full_w
-
-NSIM, NDRAW = 48, 4
-
-
-def occ3_case():
-    return examples.occ3(T=6, ngridm=30, ngridmax=100)
+from estimation_case import bits_equal
 
 
 def quantile_spec(nt, layout):
@@ -31,43 +18,22 @@ def quantile_spec(nt, layout):
     return mo.MomentSpec(items, layout=layout)
 
 
-def flag(name, default):
-    m = re.search(r'-D%s=(\d+)' % name, os.environ.get('EMU_EXTRA_FLAGS', ''))
-    return int(m.group(1)) if m else default
-
-
 if __name__ == '__main__':
-    san = os.environ.get('EMU_SANITIZE', '0')
-    m = occ3_case()
-    text = codegen.generate_modelspec(m)
-    d = os.path.join(build.MODELS_DIR, build.model_tag(m, text))
-    os.makedirs(d, exist_ok=True)
-    open(os.path.join(d, 'modelspec.h'), 'w').write(text)
-    lib = runtime.ModelLibrary(build_emu.build(d, {'0': False}.get(san, san), 1, False, 1))
-    rng = np.random.default_rng(4)
-    P = m.param_vector()[None] * (1 + 0.15 * rng.uniform(-1, 1, (NDRAW, len(m.param_vector()))))
-    s = runtime.Solver(lib, m.descriptor(), ndraw=NDRAW, keep_history=True)
-    s.set_params(P)
-    s.solve(raise_on_error=False)
-    st = s.status()[0]
-    init = np.column_stack([np.ones(NSIM), rng.uniform(m.a0, m.mmax, NSIM)])
+    b = emu.solved_batch()
+    lib, s, init, st = b.lib, b.s, b.init, b.st
     spec = quantile_spec(s.nt, lib.info)
     rec = spec.pack(s.nt, lib.info)
     nmom = len(spec)
     bad = []
-    # what the build exercises, from the arithmetic of the library (QNT_LDS_KEYS; estimation_step's slices)
+    # what the build exercises, from the arithmetic of the library (QNT_LDS_KEYS)
     q = lib.quantile_lds_keys
     if q != flag('QNT_LDS_KEYS', 2048):
         bad.append('the library reports QNT_LDS_KEYS = %d' % q)
     cand = NSIM * (rec['it_last'] - rec['it_first'] + 1)[rec['kind'] == 3]
     regimes = (int((cand <= q).sum()), int((cand > q).sum()))
-    slice_ = max(1, min(NDRAW, flag('EG_SIM_SLICE_BYTES', 2 << 30) // (8 * lib.nout * s.nt * NSIM)))
-    nslices = -(-NDRAW // slice_)
-    if 'EG_SIM_SLICE_BYTES' in os.environ.get('EMU_EXTRA_FLAGS', '') and nslices < 2:
-        bad.append('EG_SIM_SLICE_BYTES is set but the %d draws take %d slice' % (NDRAW, nslices))
-    target = rng.uniform(0, 1, nmom)
+    nslices = emu.slices(b, bad)
+    target = b.rng.uniform(0, 1, nmom)
     W = full_w(nmom)
-    orc = Oracle(m)
     solved = 0
     for rndtype in (0, 1):
         seed = 321 + rndtype
@@ -76,15 +42,13 @@ if __name__ == '__main__':
         obj = np.zeros(NDRAW)
         s.simulate_batch_spec(init, spec, seed=seed, rndtype=rndtype, target=target, W=W, means_dev=means.ctypes.data,
                               counts_dev=counts.ctypes.data, obj_dev=obj.ctypes.data)
-        rs = estimation_case.uniforms(seed, 4 * s.nt * (1 if rndtype == 1 else NSIM))
-        for dr in range(NDRAW):
-            sol = orc.solve(P[dr])
-            if sol.rc != 0:
+        for dr, sims in emu.oracle_panels(b, seed, rndtype):
+            if sims is None:
                 if st[dr] == 0 or not np.isnan(obj[dr]) or counts[dr].any() or not np.isnan(means[dr]).all():
                     bad.append('rndtype %d draw %d: oracle fails, device status %d' % (rndtype, dr, st[dr]))
                 continue
             solved += 1
-            ref_m, ref_c = spec.evaluate(orc.sim(sol, init, rs, rndtype=rndtype, params=P[dr]), block=1)
+            ref_m, ref_c = spec.evaluate(sims, block=1)
             if not np.array_equal(counts[dr], ref_c):
                 bad.append('rndtype %d draw %d: counts differ' % (rndtype, dr))
             if not bits_equal(means[dr], ref_m):

@@ -7,7 +7,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests', 'cpu_emu'))
 import build_emu
-from egdst_amd import build, codegen, runtime, workloads
+from egdst_amd import runtime, workloads
+from estimation_emu import write_modelspec
 
 if sys.argv[1] == 'unset':
     os.environ.pop('GPU_MAX_HW_QUEUES', None)   # (import egdst_amd sets a default; the library reads it when a handle is created)
@@ -15,12 +16,7 @@ else:
     os.environ['GPU_MAX_HW_QUEUES'] = sys.argv[1]
 os.environ.pop('EGDST_GROUPS', None)
 m, gen = workloads.c2(a0=0, ngridm=12, T=3, ny=3)
-text = codegen.generate_modelspec(m)
-d = os.path.join(build.MODELS_DIR, build.model_tag(m, text))
-os.makedirs(d, exist_ok=True)
-spec = os.path.join(d, 'modelspec.h')
-if not os.path.exists(spec) or open(spec).read() != text:
-    open(spec, 'w').write(text)
+d = write_modelspec(m)
 lib = runtime.ModelLibrary(build_emu.build(d, False, 1, False, 1))
 for nd in [int(a) for a in sys.argv[2:]]:
     s = runtime.Solver(lib, m.descriptor(), ndraw=nd, keep_history=False)

@@ -1,5 +1,6 @@
 """Shared by the CPU-harness test and the GPU test of the on-device estimation step (egdst_simulate_batch_moments):
-the host replay of the uniforms, the oracle's moments per draw, and the comparison."""
+the host replay of the uniforms, the oracle's moments per draw, and the comparison; and bits_equal, which every test of
+the estimation step compares floats with."""
 import warnings
 
 import numpy as np
@@ -16,6 +17,13 @@ def uniforms(seed, n):
         z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
         z = z ^ (z >> np.uint64(31))
     return (z >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def bits_equal(a, b):
+    """the same shape, the same NaN pattern and, elsewhere, the same bits"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    na, nb = np.isnan(a), np.isnan(b)
+    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
 
 
 def oracle_moments(orc, params, init, rs, rndtype):

@@ -14,6 +14,7 @@ from egdst_amd import moments as mo
 from oracle_harness import Oracle
 from test_gpu_parity import gpu_solve
 import estimation_case
+from estimation_case import bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -24,12 +25,6 @@ MODELS = {
     'occ3_n400': (lambda: examples.occ3(ngridm=400, ngridmax=4000, nthrhmax=400, ny=15), 0.0),   # nt = 41
     'retirement_mortal': (lambda: examples.retirement_mortal(), 0.5),                             # nt = 25
 }
-
-
-def bits_equal(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
 
 
 def _lag_items(nt, nch):

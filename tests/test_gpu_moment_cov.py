@@ -16,7 +16,8 @@ from egdst_amd import build, runtime, workloads
 from egdst_amd import moments as mo
 from oracle_harness import Oracle
 import estimation_case
-from test_gpu_lag_moments import MODELS, NDRAW, NSIM, SEED, _case, _index, _lag_items, bits_equal
+from estimation_case import bits_equal
+from test_gpu_lag_moments import MODELS, NDRAW, NSIM, SEED, _case, _index, _lag_items
 
 pytestmark = pytest.mark.gpu
 

@@ -12,14 +12,9 @@ from egdst_amd import moments as mo
 from oracle_harness import Oracle
 from test_gpu_parity import gpu_solve
 import estimation_case
+from estimation_case import bits_equal
 
 pytestmark = pytest.mark.gpu
-
-
-def bits_equal(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    na, nb = np.isnan(a), np.isnan(b)
-    return np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
 
 
 def _nout(s):

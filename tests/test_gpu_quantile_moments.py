@@ -12,8 +12,9 @@ from egdst_amd import examples, runtime
 from egdst_amd import moments as mo
 from oracle_harness import Oracle
 from test_gpu_parity import gpu_solve
-from test_gpu_moment_spec import _full_spec, bits_equal
+from test_gpu_moment_spec import _full_spec
 import estimation_case
+from estimation_case import bits_equal
 
 pytestmark = pytest.mark.gpu
 

@@ -79,6 +79,46 @@ def test_a_spec_without_lags_packs_the_same_either_way():
     assert not b['lag2'].any() and not b['cond_lag'].any()
 
 
+def _plain_and_lagged():
+    plain = mo.MomentSpec([mo.mean('C'), mo.cross('M', 'C', periods=(1, 3), where=('st1', 0, 1)), mo.share('id', 1, periods=2),
+                           mo.quantile('A', 0.25, where=('id', 1, 2))], layout=LAYOUT)
+    return plain, mo.MomentSpec(plain + [mo.cross('C', 'C', lag=1), mo.transition('id', 0, 1)], layout=LAYOUT)
+
+
+@pytest.mark.parametrize('form', ['spec', 'lagged spec', 'MOMENT_DTYPE', 'MOMENT_LAG_DTYPE', 'list of tuples'])
+def test_lag_records_of_what_a_caller_may_pass(form):
+    """lag_records: the records, byte for byte those of pack / pack_lag, and the entry they need -- the one that takes
+    egdst_moment_lag for a spec with a lag and for an array of MOMENT_LAG_DTYPE (zero lags or not), the other one otherwise"""
+    plain, lagged = _plain_and_lagged()
+    given, want, door = {'spec': (plain, plain.pack_lag(NT), False),
+                         'lagged spec': (lagged, lagged.pack_lag(NT), True),
+                         'MOMENT_DTYPE': (plain.pack(NT), plain.pack_lag(NT), False),
+                         'MOMENT_LAG_DTYPE': (plain.pack_lag(NT), plain.pack_lag(NT), True),
+                         'list of tuples': ([tuple(r) for r in plain.pack(NT)], plain.pack_lag(NT), False)}[form]
+    rec, lag = mo.lag_records(given, NT, layout=LAYOUT)
+    assert lag is door
+    assert rec.dtype == mo.MOMENT_LAG_DTYPE and rec.flags['C_CONTIGUOUS'] and rec.shape == (len(want),)
+    assert rec.tobytes() == want.tobytes()
+    if not door:   # what the entry without lags is sent
+        narrow = mo.convert_records(rec, mo.MOMENT_DTYPE)
+        assert narrow.dtype == mo.MOMENT_DTYPE and narrow.tobytes() == plain.pack(NT).tobytes()
+
+
+def test_convert_records_widens_with_zero_lags_and_refuses_to_drop_a_lag():
+    plain, lagged = _plain_and_lagged()
+    a, b = plain.pack(NT), plain.pack_lag(NT)
+    assert mo.convert_records(a, mo.MOMENT_LAG_DTYPE).tobytes() == b.tobytes()
+    assert mo.convert_records(b, mo.MOMENT_DTYPE).tobytes() == a.tobytes()
+    assert mo.convert_records(a, mo.MOMENT_DTYPE).tobytes() == a.tobytes() and mo.convert_records(b[::-1], mo.MOMENT_LAG_DTYPE).flags['C_CONTIGUOUS']
+    for field in ('lag2', 'cond_lag'):
+        r = b.copy()
+        r[field][len(r) - 1] = -1
+        with pytest.raises(ValueError, match='lag'):
+            mo.convert_records(r, mo.MOMENT_DTYPE)
+    with pytest.raises(ValueError, match='lag'):
+        mo.convert_records(lagged.pack_lag(NT), mo.MOMENT_DTYPE)
+
+
 @pytest.mark.parametrize('item', [
     mo.Moment(mo.MEAN, 'C', lag=1), mo.Moment(mo.SHARE, 'id', lo=1.0, hi=1.0, lag=-1), mo.Moment(mo.QUANTILE, 'C', lo=0.5, lag=2),
     mo.cross('C', 'M', lag=NT), mo.cross('C', 'M', lag=-NT), mo.mean('C', where=('id', 0, 0, NT)),

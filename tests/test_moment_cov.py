@@ -8,17 +8,12 @@ import numpy as np
 import pytest
 
 from egdst_amd import moments as mo
+from estimation_case import bits_equal
 
 LAYOUT = (1, 1, 1)            # nout = 14
 NT, NOUT = 6, 14
 INF = float('inf')
 EMPTY = 12                    # the record of _spec nothing satisfies
-
-
-def bits_equal(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a[~na].view(np.int64), b[~nb].view(np.int64))
 
 
 def _spec():
