@@ -21,6 +21,97 @@
 #define EG_A0T 0.0  // egdst_solver.c:49
 #define EG_NOUT (11 + MS_NNST + MS_NND + MS_NEQ)  // columns of a simulated path (egdst_simulate: nsimout)
 
+// ---- clock stamps (diagnostic builds) --------------------------------------------------------
+// -DEGDST_STAMPS=<set> compiles ONE set of stamps in: where the kernels of that set spend their time, in ticks of wall_clock64
+// (10 ns), and a few counters.  The sets are mutually exclusive -- a block-level stamp is a barrier, and a set's barriers would
+// show up in what another set times.  Every stamp goes to a slot of its own in Batch::stamps, EG_NSTAMP u64 per draw, zeroed at
+// the start of a solve (egdst_get_stamps reads them, egdst_stamp_names names them); Batch::dbg is left to the guards.  Without
+// the switch the macros below expand to nothing and Batch has no such array.
+//   env     k_envelope by phase: stop rule + compaction, LDS sort, walk phase; the walk's separate classification pass
+//   walk    inside env_walk_wave: regular batches against generic steps, ticks and counts
+//   seg     inside run_walk: planning the cuts, the segments (wall, sum over the waves, the longest one), check + gather; walks
+//           by one wave (ticks, how many) and why
+//   sort    inside blk_sort_lds: staging + order check, ranks, scatter
+//   wg      residency of whole k_envelope workgroups, completed cells only
+//   tpsort  throughput path, k_tp_sort: prologue and whole kernel; inside blk_rank_sort (k_envelope's global-memory sorts too):
+//           staging + order check, presort of lists out of order, ranks, tail; sorts, sorts with a list out of order
+//   tpwalk  throughput path, tp_walk per stage: set-up and load, the walk, the rest; walks
+#define EG_STAMP_SLOTS(X)                                                                                                       \
+    X(env, ENV_CLASSIFY, "env.classify") X(env, ENV_STOP, "env.stop_compact") X(env, ENV_SORT, "env.lds_sort")                    \
+    X(env, ENV_WALK, "env.walk_phase")                                                                                          \
+    X(walk, WALK_STEP, "walk.step_ticks") X(walk, WALK_BATCH, "walk.batch_ticks") X(walk, WALK_NSTEP, "walk.steps")             \
+    X(walk, WALK_NBATCH, "walk.batches")                                                                                        \
+    X(seg, SEG_PLAN, "seg.plan") X(seg, SEG_WALL, "seg.segments_wall") X(seg, SEG_GATHER, "seg.check_gather")                   \
+    X(seg, SEG_SUM, "seg.segments_sum") X(seg, SEG_LONGEST, "seg.longest_segment") X(seg, SEG_ONEWAVE, "seg.onewave_ticks")     \
+    X(seg, SEG_NONEWAVE, "seg.onewave_walks") X(seg, SEG_WHY, "seg.onewave_why")                                                 \
+    X(sort, SORT_STAGE, "sort.stage_check") X(sort, SORT_RANKS, "sort.ranks") X(sort, SORT_SCATTER, "sort.scatter")             \
+    X(wg, WG_RESIDENT, "wg.resident")                                                                                           \
+    X(tpsort, TPS_STAGE, "tpsort.stage_check") X(tpsort, TPS_PRESORT, "tpsort.presort") X(tpsort, TPS_RANKS, "tpsort.ranks")    \
+    X(tpsort, TPS_TAIL, "tpsort.tail") X(tpsort, TPS_NSORT, "tpsort.sorts") X(tpsort, TPS_NBAD, "tpsort.sorts_out_of_order")    \
+    X(tpsort, TPS_PROLOGUE, "tpsort.prologue") X(tpsort, TPS_KERNEL, "tpsort.kernel")                                           \
+    X(tpwalk, TPW_LOAD0, "tpwalk.stage0_load") X(tpwalk, TPW_WALK0, "tpwalk.stage0_walk") X(tpwalk, TPW_REST0, "tpwalk.stage0_rest") \
+    X(tpwalk, TPW_LOAD1, "tpwalk.stage1_load") X(tpwalk, TPW_WALK1, "tpwalk.stage1_walk") X(tpwalk, TPW_REST1, "tpwalk.stage1_rest") \
+    X(tpwalk, TPW_N0, "tpwalk.stage0_walks") X(tpwalk, TPW_N1, "tpwalk.stage1_walks")
+#define EG_STAMP_ENUM_(set, slot, name) EG_ST_##slot,
+enum { EG_STAMP_SLOTS(EG_STAMP_ENUM_) EG_NSTAMP };
+enum { EG_STAMPSET_env = 1, EG_STAMPSET_walk, EG_STAMPSET_seg, EG_STAMPSET_sort, EG_STAMPSET_wg, EG_STAMPSET_tpsort, EG_STAMPSET_tpwalk };
+#ifdef EGDST_STAMPS
+#define EG_STAMP_CAT_(a, b) a##b
+#define EG_STAMP_CAT(a, b) EG_STAMP_CAT_(a, b)
+#define EG_STAMP_ON(set) (EG_STAMP_CAT(EG_STAMPSET_, EGDST_STAMPS) == EG_STAMPSET_##set)
+// p: the draw's slots (Batch::stamps + EG_NSTAMP * draw, handed down as `stp` where the Batch is out of reach), may be null
+// t: a clock of the caller's, started by EG_STAMP_CLOCK and restarted by every stamp taken with it
+#define EG_STAMP_DECL(...) __VA_ARGS__                    /* declarations only a stamp build has */
+#define EG_STAMP_FIELD unsigned long long *stp;           /* ... a struct member */
+#define EG_STAMP_PARAM , unsigned long long *stp          /* ... a trailing parameter, and its argument */
+#define EG_STAMP_ARG(p) , p
+#define EG_STAMP_CLOCK(set, t) unsigned long long t = EG_STAMP_ON(set) ? wall_clock64() : 0ull
+// block level: barrier, then thread 0 adds the ticks since t to the slot (every thread of the workgroup must get here)
+#define EG_STAMP_BLOCK(set, p, slot, t)                                                  \
+    do {                                                                                 \
+        if (EG_STAMP_ON(set)) {                                                          \
+            __syncthreads();                                                             \
+            if (threadIdx.x == 0 && (p)) {                                               \
+                const unsigned long long n_ = wall_clock64();                            \
+                atomicAdd((p) + (slot), n_ - t);                                         \
+                t = n_;                                                                  \
+            }                                                                            \
+        }                                                                                \
+    } while (0)
+// wave or lane level: no barrier; the lanes for which cond holds add the ticks since t to the slot
+#define EG_STAMP_LANE(set, cond, p, slot, t)                                             \
+    do {                                                                                 \
+        if (EG_STAMP_ON(set) && (cond) && (p)) {                                         \
+            const unsigned long long n_ = wall_clock64();                                \
+            atomicAdd((p) + (slot), n_ - t);                                             \
+            t = n_;                                                                      \
+        }                                                                                \
+    } while (0)
+// the same into a local accumulator (a loop that would otherwise issue an atomic per trip)
+#define EG_STAMP_TICK(set, acc, t)                                                       \
+    do {                                                                                 \
+        if (EG_STAMP_ON(set)) {                                                          \
+            const unsigned long long n_ = wall_clock64();                                \
+            acc += n_ - t;                                                               \
+            t = n_;                                                                      \
+        }                                                                                \
+    } while (0)
+// counters: add v to the slot / raise the slot to v
+#define EG_STAMP_ADD(set, cond, p, slot, v) do { if (EG_STAMP_ON(set) && (cond) && (p)) atomicAdd((p) + (slot), (unsigned long long)(v)); } while (0)
+#define EG_STAMP_MAX(set, cond, p, slot, v) do { if (EG_STAMP_ON(set) && (cond) && (p)) atomicMax((p) + (slot), (unsigned long long)(v)); } while (0)
+#else
+#define EG_STAMP_DECL(...)
+#define EG_STAMP_FIELD
+#define EG_STAMP_PARAM
+#define EG_STAMP_ARG(p)
+#define EG_STAMP_CLOCK(set, t)
+#define EG_STAMP_BLOCK(set, p, slot, t)
+#define EG_STAMP_LANE(set, cond, p, slot, t)
+#define EG_STAMP_TICK(set, acc, t)
+#define EG_STAMP_ADD(set, cond, p, slot, v)
+#define EG_STAMP_MAX(set, cond, p, slot, v)
+#endif
+
 // ---- problem geometry shared by all kernels -------------------------------------------------
 struct Geom {
     int t0, T, nt, ngridm, ngridmax, nthrhmax, ny, ndraw, nslots, S;  // S = ngridmax+1 (logical rows of a table)
@@ -92,6 +183,7 @@ struct Batch {
     double *obj;          // [2*ndraw] staging of k_objective for the host-returning entry point
     unsigned long long *algbytes;  // [ndraw] compulsory table traffic: 24 B per next-period row read once per
                                    // period + 24 B per row written + 16 B per threshold
+    EG_STAMP_DECL(unsigned long long *stamps;)  // [EG_NSTAMP*ndraw] clock stamps of the set compiled in (stamp builds only)
 };
 
 // Kernels do not take the Batch by value: ~600 bytes and ~70 pointers in the kernel-argument segment are loaded into SGPRs
@@ -308,13 +400,13 @@ static __device__ __forceinline__ Tab eg_tab(BatchRef b, int slot, int draw, int
 }
 
 // Next-period value at nxt->cash (valuefunc, egdst_solver.c:755-772 with linter_extrap, egdst_lib.c:179-206).
-// ibr: -1, or the bracket linter's search found for the same x over (M, len) when the column is known to be non-decreasing
+// ilin: -1, or the bracket linter's search found for the same x over (M, len) when the column is known to be non-decreasing
 // and len >= 4: valuefunc's search over the column shifted by one row then follows from it (k_grid_lds, eg_second_bracket).
 // verr: set when the table has fewer than two rows beside the a0 row and the analytic branch does not apply: linter_extrap then
 // reports "At least two points are required for interpolation!" (egdst_lib.c:183) and the solver returns at once
 // (egdst_solver.c:567-568).  A table of one row is what the envelope of a guess stream that ended in the generator's resend fixed
 // point leaves behind (C2 with a0 = -5: ~6 % of the parameter draws).
-template <class TT> static __device__ __forceinline__ double eg_next_value(const ms_env *E, const TT &t, const ms_pv *nxt, int ibr = -1, int *verr = nullptr)
+template <class TT> static __device__ __forceinline__ double eg_next_value(const ms_env *E, const TT &t, const ms_pv *nxt, int ilin = -1, int *verr = nullptr)
 {
     const double evf1 = t.V[0], a0 = E->a0, x = nxt->cash;
     if (x < t.M[1] && evf1 > -INFINITY) return ms_utility(E, nxt, x - a0) + ms_discount(E, nxt) * evf1;
@@ -324,7 +416,7 @@ template <class TT> static __device__ __forceinline__ double eg_next_value(const
         if (verr) *verr = 1;
         return -1.0;
     }
-    int i = (ibr >= 0) ? ((x < t.M[2]) ? 0 : ((x >= t.M[t.len - 2]) ? t.len - 3 : ibr - 1)) : eg_bracket(x, g, n, 0);
+    int i = (ilin >= 0) ? ((x < t.M[2]) ? 0 : ((x >= t.M[t.len - 2]) ? t.len - 3 : ilin - 1)) : eg_bracket(x, g, n, 0);
     double f0 = f[i], f1 = f[i + 1];
     if (!isfinite(f0)) return f0;
     if (!isfinite(f1)) return f1;

@@ -64,6 +64,7 @@ template <int L> struct EnvCtxT {
     int pm;         // function that is currently the max ((int)oix[oj-1])
     int ci;         // the reference's `ci` (persists across iterations)
     int *dbg;       // [16] diagnostics of a tripped guard
+    EG_STAMP_FIELD  // the draw's clock stamps (stamp builds)
     double *klog;   // kink log of this cell (the gateway's dbgout, egdst_solver.c:1866-1879): 4 doubles per recorded kink
     int *kcnt;      // -- (choice whose secondary envelope runs or -1, threshold, consumption left, right); nullptr: off
     int kcap;
@@ -1276,13 +1277,6 @@ template <int L> static __device__ __forceinline__ int env_count_before(const En
     return lo;
 }
 
-template <int L> static __device__ __forceinline__ double env_fn_at(EnvCtxT<L> &e, int j, int curj, double x)
-{
-    if (curj >= 0) return env_seg(e, j, curj, x, 0);
-    if (env_evf(e, j) == -INFINITY) return -INFINITY;
-    return env_analytic(e, j, x);
-}
-
 // value of function j at x given that cj of its points precede the position (wave walk; no bounds guards: below the
 // bound every function still has a point ahead, so cj <= dims[j]-1)
 template <int L> static __device__ __forceinline__ double env_fn_cnt(EnvCtxT<L> &e, int j, int cj, double x)
@@ -1398,12 +1392,8 @@ static __device__ __forceinline__ void env_walk_wave(EnvCtxT<L> &e, int npts, in
     // prediction of the segmented walk) classifies the stream again first.
     constexpr bool CDEFER = ENV_CDEFER(L);
     typename EgMem<L>::I *const clsw = const_cast<typename EgMem<L>::I *>(e.cls);
-#ifdef EGDST_STAMPS
-    unsigned long long w_t0 = wall_clock64(), w_step = 0, w_batch = 0, w_nstep = 0, w_nbatch = 0;
-#define WSTAMP(acc, cnt) do { unsigned long long n_ = wall_clock64(); acc += n_ - w_t0; w_t0 = n_; cnt++; } while (0)
-#else
-#define WSTAMP(acc, cnt)
-#endif
+    EG_STAMP_CLOCK(walk, w_t0);
+    EG_STAMP_DECL(unsigned long long w_step = 0, w_batch = 0, w_nstep = 0, w_nbatch = 0;)
     bool chain = false;  // the position after a generic step is irregular too (decided below): step again, the cursors are in place
     while (i < p1 && !e.err) {
         bool step_now = true;
@@ -1516,7 +1506,8 @@ static __device__ __forceinline__ void env_walk_wave(EnvCtxT<L> &e, int npts, in
             if (CDEFER && valid && lane < stop && !out) clsw[p] = -1;  // consumed, no row
             i += stop;
             step_now = stop < nvalid;
-            WSTAMP(w_batch, w_nbatch);
+            EG_STAMP_TICK(walk, w_batch, w_t0);
+            EG_STAMP_DECL(w_nbatch++;)
             if (step_now || !(i < p1)) break;
             }
             if (tail || step_now) {  // the sequential tail / an irregular position: the generic step needs the per-function cursors, a lane each
@@ -1545,7 +1536,8 @@ static __device__ __forceinline__ void env_walk_wave(EnvCtxT<L> &e, int npts, in
             if (CDEFER && lane == 0) clsw[i] = -1;  // (whatever row the step kept, it wrote whole)
             i++;
             if (phase == 0 && e.oj > 0) phase = 1;
-            WSTAMP(w_step, w_nstep);
+            EG_STAMP_TICK(walk, w_step, w_t0);
+            EG_STAMP_DECL(w_nstep++;)
             // Events come in clusters -- where a choice list folds, and along the whole stream when the pieces of a re-based guess
             // stream lie within ulps of each other (hundreds of crossings in a row: the slowest walk of nearly every launch,
             // profiles/r04_*).  Going back to the batches after every step costs a classification of 64 positions that commits
@@ -1574,12 +1566,9 @@ static __device__ __forceinline__ void env_walk_wave(EnvCtxT<L> &e, int npts, in
     e.pm = pm;
     e.lastg = lastg;
     e.iend = i;
-#if defined(EGDST_STAMPS) && !defined(EGDST_STAMPS2) && !defined(EGDST_STAMPS3)
-    if (lane == 0 && e.dbg) {
-        atomicAdd((unsigned long long *)e.dbg + 3, (w_nbatch << 32) | w_nstep);
-        atomicAdd((unsigned long long *)e.dbg + 4, w_step);
-        atomicAdd((unsigned long long *)e.dbg + 7, w_batch);
-    }
-#endif
+    EG_STAMP_ADD(walk, lane == 0, e.stp, EG_ST_WALK_STEP, w_step);
+    EG_STAMP_ADD(walk, lane == 0, e.stp, EG_ST_WALK_BATCH, w_batch);
+    EG_STAMP_ADD(walk, lane == 0, e.stp, EG_ST_WALK_NSTEP, w_nstep);
+    EG_STAMP_ADD(walk, lane == 0, e.stp, EG_ST_WALK_NBATCH, w_nbatch);
 #endif
 }

@@ -475,6 +475,7 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
         {(void **)&b.tpn, sizeof(int) * EGDST_MAX_GROUPS * g.nt}, {(void **)&b.tplist, sizeof(int) * nds},
         {(void **)&b.tpbign, sizeof(int) * EGDST_MAX_GROUPS * g.nt}, {(void **)&b.tpbiglist, sizeof(int) * nds},
         {(void **)&b.tpstat, sizeof(unsigned) * 2 * ndraw},
+        EG_STAMP_DECL({(void **)&b.stamps, sizeof(unsigned long long) * EG_NSTAMP * ndraw},)
 #if MS_ND == 1
         {(void **)&b.e1tiles, sizeof(Env1Tile) * nds * EG_E1_NB(d->ngridm)}, {(void **)&b.e1done, sizeof(unsigned) * nds},
 #endif
@@ -962,6 +963,7 @@ static int enqueue_solve(egdst_handle *h)
     HIPCHK(hipMemsetAsync(b.evals, 0, sizeof(unsigned long long) * g.ndraw, s));
     HIPCHK(hipMemsetAsync(b.credited, 0, sizeof(unsigned long long) * g.ndraw, s));
     HIPCHK(hipMemsetAsync(b.segstat, 0, sizeof(unsigned) * 2 * g.ndraw, s));
+    EG_STAMP_DECL(HIPCHK(hipMemsetAsync(b.stamps, 0, sizeof(unsigned long long) * EG_NSTAMP * g.ndraw, s));)
     HIPCHK(hipMemsetAsync(b.algbytes, 0, sizeof(unsigned long long) * g.ndraw, s));
     HIPCHK(hipMemsetAsync(b.tlen, 0, sizeof(int) * (size_t)g.nslots * g.ndraw * MS_NST, s));
     HIPCHK(hipMemsetAsync(b.tthlen, 0, sizeof(int) * (size_t)g.nslots * g.ndraw * MS_NST, s));
@@ -1829,6 +1831,28 @@ extern "C" int egdst_get_debug(egdst_handle *h, int draw, int *out16)
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out16, h->b.dbg + 16 * draw, sizeof(int) * 16, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// Clock stamps of a diagnostic build (egdst_device.h): the names of the slots, the same table in every build, and one draw's
+// slots as the last solve left them -- which only a library built with -DEGDST_STAMPS=<set> has.
+extern "C" int egdst_stamp_names(const char **names, int cap)
+{
+#define EG_STAMP_NAME_(set, slot, name) name,
+    static const char *const tab[EG_NSTAMP] = {EG_STAMP_SLOTS(EG_STAMP_NAME_)};
+    for (int i = 0; names && i < cap && i < EG_NSTAMP; i++) names[i] = tab[i];
+    return EG_NSTAMP;
+}
+
+extern "C" int egdst_get_stamps(egdst_handle *h, int draw, unsigned long long *out)
+{
+    if (!h || !out || draw < 0 || draw >= h->b.g.ndraw) return set_err(EGDST_E_ARG, "egdst_get_stamps: bad arguments");
+#ifdef EGDST_STAMPS
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, h->b.stamps + (size_t)EG_NSTAMP * draw, sizeof(unsigned long long) * EG_NSTAMP, hipMemcpyDeviceToHost));
+    return 0;
+#else
+    return set_err(EGDST_E_ARG, "egdst_get_stamps: this library was built without -DEGDST_STAMPS=<set>");
+#endif
 }
 
 extern "C" int egdst_device_tables(egdst_handle *h, int it, const double **M_dev, const double **C_dev,

@@ -1181,46 +1181,19 @@ static __device__ __forceinline__ int eg_second_bracket(double x, int i, double 
     return (x < m2) ? 0 : ((x >= mlast2) ? n1 - 3 : i - 1);
 }
 
-// eg_bracket(x, g, n, 0) on a NON-DECREASING column, starting from a hint: the bracket of a neighbouring asset point for the
-// same next state and shock node.  The search returns the last row i in [1, n-3] with g[i] <= x (0 below g[1], n-2 from
-// g[n-2] on), which on an ordered column is unique -- however it is found.  Cash-in-hand moves by less than a table row or two
-// from one asset point to the next, so a step or two from the neighbour's bracket replaces log2(n) dependent reads; after
-// EG_NEAR_STEPS steps (the hint was far off) or for a NaN the full search decides.
-#ifndef EG_NEAR_STEPS
-#define EG_NEAR_STEPS 6
-#endif
-template <class P> static __device__ __forceinline__ int eg_bracket_near(double x, P g, int n, int hint)
-{
-    if (x < g[1]) return 0;
-    if (x >= g[n - 2]) return n - 2;
-    int i = min(max(hint, 1), n - 3);
-    if (g[i] <= x) {
-        for (int k = 0; k < EG_NEAR_STEPS; k++) {
-            if (!(g[i + 1] <= x)) return i;  // (i + 1 <= n - 2 and x < g[n-2]: the scan stays inside)
-            i++;
-        }
-    } else if (g[i] > x) {
-        for (int k = 0; k < EG_NEAR_STEPS; k++) {
-            i--;
-            if (g[i] <= x) return i;         // (g[1] <= x: the scan stops at row 1 at the latest)
-        }
-    }
-    return eg_bracket(x, g, n, 0);
-}
-
-// eg_term + eg_next_value for keep == 1 with the M column in LDS and one search (see above).  ibr: nullptr, or in: the
-// bracket of the neighbouring asset point (< 0: none), out: this point's.
+// eg_term + eg_next_value for keep == 1 with the M column in LDS and one search (see above).  The staged column is known to
+// be in order (the caller checked while staging): the branch-free search.
 // TT: Tab (C and V in global memory) or TabL (staged in LDS as well, k_grid_lds_cv)
-// sorted: the staged column is known to be in order (the callers' fast path): the branch-free search
+// (Measured slower and removed with the several-points-per-lane form of the grid kernel, egdst_host.inc: enqueue_grid -- a search
+//  that starts from the bracket of the lane's previous point, a step or two along the column instead of log2(n) reads.)
 template <class TT>
 static __device__ __forceinline__ double eg_term_lds(const ms_env *E, const eg_ldsd *M, const TT &t, const ms_pv *cur, ms_pv *nxt,
-                                                     double pr1, double *t_rhs, double *t_evf, int *ibr = nullptr, int sorted = 0)
+                                                     double pr1, double *t_rhs, double *t_evf)
 {
     nxt->cash = ms_cashinhand(E, cur, nxt);
     const double x = nxt->cash;
     const int n1 = t.len;
-    const int i = (ibr && *ibr >= 0) ? eg_bracket_near(x, M, n1, *ibr) : (sorted ? eg_bracket_sorted(x, M, n1) : eg_bracket(x, M, n1, 0));
-    if (ibr) *ibr = i;
+    const int i = eg_bracket_sorted(x, M, n1);
     const double mlast = M[n1 - 1], mfirst = M[1];
     // rows i and i+1 of C and of V in ONE round of global reads: away from the table's ends valuefunc's bracket is the same
     // pair of rows (j+1 == i below), and a lane that waits twice per evaluation waits half as often
@@ -1285,14 +1258,12 @@ static __device__ __forceinline__ int eg_bracket_sampled(double x, const eg_ldsd
 
 static __device__ __forceinline__ double eg_term_sampled(const ms_env *E, const eg_ldsd *S, int ns, int stride, const eg_ldsd *edge,
                                                          const Tab &t, const ms_pv *cur, ms_pv *nxt, double pr1, double *t_rhs,
-                                                         double *t_evf, int *ibr = nullptr)
+                                                         double *t_evf)
 {
     nxt->cash = ms_cashinhand(E, cur, nxt);
     const double x = nxt->cash;
     const int n1 = t.len;
-    // (with a neighbour's bracket at hand: a step or two in the global column, the lines the neighbour just read)
-    const int i = (ibr && *ibr >= 0) ? eg_bracket_near(x, t.M, n1, *ibr) : eg_bracket_sampled(x, S, ns, stride, t.M, n1, edge);
-    if (ibr) *ibr = i;
+    const int i = eg_bracket_sampled(x, S, ns, stride, t.M, n1, edge);
     const double mlast = edge[3], mfirst = edge[0];
     // (rows i and i+1 of M, C and V in one round of global reads, see eg_term_lds)
     const double Mi = t.M[i], Mi1 = t.M[i + 1], Ci = t.C[i], Ci1 = t.C[i + 1], Vi = t.V[i], Vi1 = t.V[i + 1];
@@ -1354,11 +1325,12 @@ __global__ void __launch_bounds__(GRID_BS) k_sortcheck(const Batch *bp_, int it)
 #ifndef GRID_MINW
 #define GRID_MINW 1  // (experiments: waves per SIMD k_grid_lds is compiled for; 8 = at most 64 VGPRs)
 #endif
-// PPL: consecutive asset points per lane.  1: a lane per point.  More (batches with points to spare): the lane evaluates its
-// points side by side -- (next state, shock node) outside, the points inside, every point with its own sums, so the order of
-// accumulation per point is the reference's -- and a point starts its bracket search from its predecessor's bracket
-// (eg_bracket_near): the verdict of round 2 on this kernel was "issue-bound on integer work", four of five issue slots
-// address arithmetic and compares of searches that land a row or two from where the neighbouring point's search landed.
+// PPL: consecutive asset points per lane.  Both kernels below pass 1, a lane per point.  More: the lane evaluates its points
+// side by side -- (next state, shock node) outside, the points inside, every point with its own sums, so the order of
+// accumulation per point is the reference's.  (Measured slower and removed: k_grid_lds_n with PPL > 1, where a point started
+// its bracket search from its predecessor's bracket -- C2 x 4096 194.4 ms against 184.8 with a lane per point, C4 x 32 52.6
+// against 51.5, C5 x 128 3.72 s either way.  The per-point arrays and loops stay: written out for one point, the same
+// statements compile to other device code, profiles/r07_device_code_identity.txt.)
 // CV: the C and V columns are staged too (whole columns only; the dynamic LDS then holds 3 x lrows doubles): no global read is
 // left in the loop over (next state, shock node) -- k_grid_lds_cv, below
 template <int PPL, bool CV = false> static __device__ __forceinline__ void eg_grid_lds_body(BatchRef b, int it, int lrows)
@@ -1535,7 +1507,6 @@ template <int PPL, bool CV = false> static __device__ __forceinline__ void eg_gr
             const int ns = gl_ns[nxt.ist];
             const eg_ldsd *edge = (const eg_ldsd *)gl_edge + 4 * nxt.ist;
             for (int iy = 0; iy < niymax; iy++) {
-                int hint = -1;  // the bracket of the previous point of this lane for this (state, node)
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
                     if (done[j] || iy >= niyj[j]) continue;
@@ -1554,10 +1525,10 @@ template <int PPL, bool CV = false> static __device__ __forceinline__ void eg_gr
                         TabL tl;
                         tl.M = M, tl.C = (const eg_ldsd *)LC + gl_off[nxt.ist], tl.V = (const eg_ldsd *)LV + gl_off[nxt.ist];
                         tl.TH = t.TH, tl.D = t.D, tl.len = t.len, tl.thlen = t.thlen;
-                        c1[j] = eg_term_lds(&E, M, tl, &cur, &nxt, pr1, &t_rhs, &t_evf, PPL > 1 ? &hint : nullptr, 1);
+                        c1[j] = eg_term_lds(&E, M, tl, &cur, &nxt, pr1, &t_rhs, &t_evf);
                     } else
-                    c1[j] = (stride > 1) ? eg_term_sampled(&E, M, ns, stride, edge, t, &cur, &nxt, pr1, &t_rhs, &t_evf, PPL > 1 ? &hint : nullptr)
-                                         : eg_term_lds(&E, M, t, &cur, &nxt, pr1, &t_rhs, &t_evf, PPL > 1 ? &hint : nullptr, 1);
+                    c1[j] = (stride > 1) ? eg_term_sampled(&E, M, ns, stride, edge, t, &cur, &nxt, pr1, &t_rhs, &t_evf)
+                                         : eg_term_lds(&E, M, t, &cur, &nxt, pr1, &t_rhs, &t_evf);
                     if (c1[j] > 0) {
                         rhs[j] += t_rhs;
                         evf[j] += t_evf;
@@ -1986,7 +1957,7 @@ static __device__ __forceinline__ void eg_merge2_classify(int npts, int nf, int 
 template <class ANA>
 static __device__ __forceinline__ void blk_rank_sort(int npts, int nf, const double *im, const double *ic, const double *iv, const int *ifn,
                                      const eg_ldsi *fstart, const eg_ldsi *dims, double *om, double *oc, double *ov, int *of,
-                                     int *rank, int *sh, int *oob, int *dbg, int *cls, int *fused, ANA ana, eg_ldsd *lkeys,
+                                     int *rank, int *sh, int *oob, int *dbg EG_STAMP_PARAM, int *cls, int *fused, ANA ana, eg_ldsd *lkeys,
                                      int lkeys_cap, eg_ldss *lperm = nullptr, eg_ldsi *lcls = nullptr, int lperm_cap = 0)
 {
     // The sorted stream is written in TWO steps.  A point's rank is where it goes, and neighbouring threads hold neighbouring
@@ -2006,14 +1977,7 @@ static __device__ __forceinline__ void blk_rank_sort(int npts, int nf, const dou
     // (32 B per point) often still fits with its M keys alone (8 B per point: C3's 12 000-point primary stream, 96 KB):
     // the binary searches of the rank merge then run on LDS, and the V keys are read from global memory only at M ties
     // and at the bracket of the classification.
-#ifdef EGDST_TPSTAMPS  // diagnostic: where a global-memory sort spends its time (dbg as 8 x u64: 0 staging + order check, 1 presort
-    unsigned long long tp_t_ = wall_clock64();  // of lists out of order, 2 ranks, 3 tail; 4 sorts, 5 sorts with a list out of order)
-#define TPST(k) do { __syncthreads(); if (threadIdx.x == 0 && dbg) { const unsigned long long n_ = wall_clock64(); atomicAdd((unsigned long long *)dbg + (k), n_ - tp_t_); tp_t_ = n_; } } while (0)
-#define TPCNT(k, v) do { if (threadIdx.x == 0 && dbg) atomicAdd((unsigned long long *)dbg + (k), (unsigned long long)(v)); } while (0)
-#else
-#define TPST(k)
-#define TPCNT(k, v)
-#endif
+    EG_STAMP_CLOCK(tpsort, tp_t_);  // where a global-memory sort spends its time
     const bool lds_keys = lkeys != nullptr && npts <= lkeys_cap;
     // (longer still: every sk-th key, a sampled index -- see eg_rank_classify_run)
     const int sk = (lkeys != nullptr && !lds_keys && lkeys_cap >= 64) ? (npts + lkeys_cap - 1) / lkeys_cap : 0;
@@ -2029,9 +1993,9 @@ static __device__ __forceinline__ void blk_rank_sort(int npts, int nf, const dou
         if (ifn[i] == ifn[i - 1] && !pt_before(im[i - 1], iv[i - 1], ifn[i - 1], i - 1, im[i], iv[i], ifn[i], i)) bad = 1;
     bad = blk_sum(bad, sh);
     EG_CENSUS_BAD(bad ? 1 : 0);
-    TPST(0);
-    TPCNT(4, 1);
-    TPCNT(5, bad ? 1 : 0);
+    EG_STAMP_BLOCK(tpsort, stp, EG_ST_TPS_STAGE, tp_t_);  // staging + order check
+    EG_STAMP_ADD(tpsort, threadIdx.x == 0, stp, EG_ST_TPS_NSORT, 1);
+    EG_STAMP_ADD(tpsort, threadIdx.x == 0, stp, EG_ST_TPS_NBAD, bad ? 1 : 0);
     if (bad) {
         // A list out of comp1 order is out of order LOCALLY: the double point of a kink (x + 1e-10) has overtaken the next
         // grid point or two -- on fine grids (C5: 32 768 points, spacing below 1e-10 near a0) that happens in many periods,
@@ -2124,7 +2088,7 @@ static __device__ __forceinline__ void blk_rank_sort(int npts, int nf, const dou
             networked = true;
         }
     }
-    TPST(1);
+    EG_STAMP_BLOCK(tpsort, stp, EG_ST_TPS_PRESORT, tp_t_);  // presort of lists out of order
     double kbound = INFINITY;  // min over the functions of their last grid value (:1266-1271)
     *fused = 0;
     if (!bad && cls) {
@@ -2205,7 +2169,7 @@ static __device__ __forceinline__ void blk_rank_sort(int npts, int nf, const dou
             }
         }
     }
-    TPST(2);
+    EG_STAMP_BLOCK(tpsort, stp, EG_ST_TPS_RANKS, tp_t_);
     for (int i = threadIdx.x; i < npts && bad && !networked; i += ENV_BS) {  // (lists still out of order after the presort: counting)
         const double m = im[i], v = iv[i];
         const int f = ifn[i];
@@ -2277,7 +2241,7 @@ static __device__ __forceinline__ void blk_rank_sort(int npts, int nf, const dou
         }
         __syncthreads();
     }
-    TPST(3);
+    EG_STAMP_BLOCK(tpsort, stp, EG_ST_TPS_TAIL, tp_t_);
 #ifdef EGDST_VERIFY_SORT
     // diagnostic build: the output must be a permutation of the input in comp1 order
     for (int i = threadIdx.x; i < npts && !bad; i += ENV_BS) {
@@ -2315,19 +2279,11 @@ static __device__ __forceinline__ eg_ldss *blk_sort_lds(int npts, int nf, const 
                                                         const double *iv, const int *ifn, const eg_ldsi *fstart,
                                                         const eg_ldsi *dims, eg_ldsd *R1, eg_ldsd *R2, eg_ldsd *R3,
                                                         eg_ldss *Lf, eg_ldss *Lp, int lcap, int *sh, int *oob,
-                                                        eg_ldsi *cls, int *fused, ANA ana, int *dbg = nullptr)
+                                                        eg_ldsi *cls, int *fused, ANA ana, int *dbg EG_STAMP_PARAM)
 {
     eg_ldsd *Km = R1, *Kv = R2, *Lm = R2, *Lv = R3, *Lc = R1;
     const int tid = threadIdx.x;
-#ifdef EGDST_EXP_NOCLS  // experiment: ranks only, the walk classifies
-    cls = nullptr;
-#endif
-#ifdef EGDST_STAMPS3  // diagnostic: staging + order check (slot 3), ranks (4), scatter (7)
-    unsigned long long t3_ = wall_clock64();
-#define ST3(k) do { __syncthreads(); if (tid == 0 && dbg) { const unsigned long long n_ = wall_clock64(); atomicAdd((unsigned long long *)dbg + (k), n_ - t3_); t3_ = n_; } } while (0)
-#else
-#define ST3(k)
-#endif
+    EG_STAMP_CLOCK(sort, t3_);
     *fused = 0;
     for (int i = tid; i < npts; i += ENV_BS) {
         Km[i] = im[i];
@@ -2342,7 +2298,7 @@ static __device__ __forceinline__ eg_ldss *blk_sort_lds(int npts, int nf, const 
     while (P < npts) P <<= 1;
     if (bad && P > lcap) bad = 2;  // no room for the padded network: counting ranks instead
     EG_CENSUS_BAD(bad);
-    ST3(3);
+    EG_STAMP_BLOCK(sort, stp, EG_ST_SORT_STAGE, t3_);  // staging + order check
     if (bad != 1) {
         double kbound = INFINITY;  // min over the functions of their last grid value (:1266-1271)
         if (!bad && cls) {
@@ -2360,9 +2316,6 @@ static __device__ __forceinline__ eg_ldss *blk_sort_lds(int npts, int nf, const 
                 if (nact == 1) gb = g;
                 nact++;
             }
-#ifdef EGDST_NO_MERGE2
-        nact = 0;
-#endif
         if (!bad && nact == 2) {
             auto emit = [&](int r, int i, int f, double m, double v, int w) {
                 if (cls) cls[r] = w;
@@ -2422,7 +2375,7 @@ static __device__ __forceinline__ eg_ldss *blk_sort_lds(int npts, int nf, const 
             Lp[i] = r;
         }
         __syncthreads();  // every rank is known
-        ST3(4);
+        EG_STAMP_BLOCK(sort, stp, EG_ST_SORT_RANKS, t3_);
         if (*oob) return Lp;
         for (int i = tid; i < npts; i += ENV_BS) Lv[Lp[i]] = Kv[i];  // R2 -> R3
         __syncthreads();
@@ -2430,7 +2383,7 @@ static __device__ __forceinline__ eg_ldss *blk_sort_lds(int npts, int nf, const 
         __syncthreads();
         for (int i = tid; i < npts; i += ENV_BS) Lc[Lp[i]] = ic[i];  // -> R1 (M keys are consumed)
         __syncthreads();
-        ST3(7);
+        EG_STAMP_BLOCK(sort, stp, EG_ST_SORT_SCATTER, t3_);
         if (!bad) return Lp;
     } else {
         // bitonic network on (Km, Kv, Lf = function, Lp = input index); padding sorts last
@@ -2541,6 +2494,7 @@ struct WalkJob {  // what one envelope walk needs besides the sorted stream
     const eg_ldsd *evfa0;
     eg_ldsi *stack;
     int *dbg;
+    EG_STAMP_FIELD
     int noseg;     // 1: never cut the walk into segments (EGDST_NOSEG; tests compare both ways)
     unsigned *segstat;  // [2] of the draw: segmented walks merged / fallen back
     int *sh;            // the workgroup's LDS scratch for scans ([ENV_MAXBS] ints)
@@ -2553,10 +2507,9 @@ struct WalkJob {  // what one envelope walk needs besides the sorted stream
 };
 
 // All threads pre-classify the sorted stream, then wave 0 walks it; results through *err, *n, *nth (valid in wave 0,
-// every lane of it holds the same values)
-// SEG = false: the walk is never cut into segments -- the throughput path (k_tp_walk), where a whole cell belongs to one
-// wave and the batch, not the cell, provides the parallelism; the planning, checking and gathering code is compiled out.
-template <int L, bool SEG = true>
+// every lane of it holds the same values).  A stream that is long enough is cut into segments that the waves walk side by side
+// (below); EGDST_SEQ_WALK compiles the planning out, Batch::noseg turns it off at run time.
+template <int L>
 static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &j, const typename EgMem<L>::D *m,
                                                 const typename EgMem<L>::DC *c, const typename EgMem<L>::D *v,
                                                 const typename EgMem<L>::S *f, const typename EgMem<L>::S *posl,
@@ -2593,6 +2546,7 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
     e.cap = j.cap;
     e.npts = j.npts;
     e.dbg = j.dbg;
+    EG_STAMP_DECL(e.stp = j.stp;)
     e.klog = j.klog;
     e.kcnt = j.kcnt;
     e.kcap = j.kcap;
@@ -2603,9 +2557,7 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
     e.oi = e.oj = 0;
     e.lastg = 0;
     e.pm = -1;
-#ifdef EGDST_STAMPS
-    const unsigned long long pc0_ = wall_clock64();
-#endif
+    EG_STAMP_CLOCK(env, pc0_);
     if (!classified) env_preclass(e, j.npts, cls, (int)threadIdx.x, ENV_BS);  // (else done by the sort)
     __syncthreads();
 #ifdef EGDST_EMU
@@ -2630,9 +2582,7 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
         }
     }
 #endif
-#ifdef EGDST_STAMPS
-    if (threadIdx.x == 0 && j.dbg) atomicAdd((unsigned long long *)j.dbg + 1, wall_clock64() - pc0_);
-#endif
+    EG_STAMP_LANE(env, threadIdx.x == 0, j.stp, EG_ST_ENV_CLASSIFY, pc0_);
     // ---- segmented walk ----------------------------------------------------------------------------------------
     // The walk is a state machine over the sorted positions, but its state after a position is small -- the current max
     // function and the grid value of the last output row (the cursors are rebuilt from counts at every event) -- and
@@ -2652,32 +2602,25 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
     // slice of the cursor arrays per walking wave, and how many waves that leaves room for
     const int slice = (j.nf + 2 <= j.slice0) ? j.slice0 : ((j.nf + 2 + 31) / 32) * 32;
     const int ww = min(min(ENV_BS / WAVE, ENV_MAXWW), j.curcap / slice);
-#ifdef EGDST_STAMPS2
-    unsigned long long s2_ = wall_clock64();
-#define STAMP2(k) do { __syncthreads(); if (tid_ == 0 && j.dbg) { const unsigned long long n_ = wall_clock64(); atomicAdd((unsigned long long *)j.dbg + (k), n_ - s2_); s2_ = n_; } } while (0)
-#else
-#define STAMP2(k)
-#endif
+    EG_STAMP_CLOCK(seg, s2_);
 #if !defined(EGDST_SEQ_WALK)
-    if (SEG) {
-        // more segments than waves: the walking waves (at most ENV_MAXWW: the slices of the cursor arrays) take them from
-        // a queue, which evens out what the cost estimate below gets wrong
-        nseg = (ENV_BS / WAVE >= 2) ? ENV_MAXSEG : 1;
-        while (nseg > 1 && j.npts < ENV_SEG_MINPTS * nseg) nseg--;  // (a segment should be worth a few batches)
-        // every segment writes its rows and thresholds into a region of its own in scratch arrays (rows: up to twice its
-        // points plus 64; thresholds: the last 2*thcap entries, thstride per segment -- nthrhmax of them when there is
-        // room, fewer otherwise: a segment that runs out of its share only sends the walk back to one wave)
-        if (j.klog || !j.wM || ww < 2 || nseg < 2) nseg = 1;
-        {
-            const long long room = ((long long)j.wcap - 2 * (long long)j.npts - 64 * nseg - 2) / 2;
-            thcap = (int)(room < (long long)j.nthrhmax ? (room > 0 ? room : 0) : (long long)j.nthrhmax);
-        }
-        while (nseg > 1 && thcap / nseg < 8) nseg--;
-        thstride = thcap / nseg;
-        if (j.noseg) nseg = 1, thstride = j.nthrhmax;
+    // more segments than waves: the walking waves (at most ENV_MAXWW: the slices of the cursor arrays) take them from
+    // a queue, which evens out what the cost estimate below gets wrong
+    nseg = (ENV_BS / WAVE >= 2) ? ENV_MAXSEG : 1;
+    while (nseg > 1 && j.npts < ENV_SEG_MINPTS * nseg) nseg--;  // (a segment should be worth a few batches)
+    // every segment writes its rows and thresholds into a region of its own in scratch arrays (rows: up to twice its
+    // points plus 64; thresholds: the last 2*thcap entries, thstride per segment -- nthrhmax of them when there is
+    // room, fewer otherwise: a segment that runs out of its share only sends the walk back to one wave)
+    if (j.klog || !j.wM || ww < 2 || nseg < 2) nseg = 1;
+    {
+        const long long room = ((long long)j.wcap - 2 * (long long)j.npts - 64 * nseg - 2) / 2;
+        thcap = (int)(room < (long long)j.nthrhmax ? (room > 0 ? room : 0) : (long long)j.nthrhmax);
     }
+    while (nseg > 1 && thcap / nseg < 8) nseg--;
+    thstride = thcap / nseg;
+    if (j.noseg) nseg = 1, thstride = j.nthrhmax;
 #endif
-    if (SEG && nseg > 1) {
+    if (nseg > 1) {
         // Where to cut: segments of equal COST, not of equal length.  A regular stretch costs ~1/64 of a batch per position,
         // a crossing several batches, and crossings cluster (the folds of a choice list sit in a narrow range of M).  The
         // number of crossings in a stretch is estimated by how often the function of consecutive points that nothing lies
@@ -2751,8 +2694,8 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
         __syncthreads();
         nseg = sg_n;
     }
-    STAMP2(3);  // planning: cost scan, cuts
-    if (SEG && nseg > 1) {
+    EG_STAMP_BLOCK(seg, j.stp, EG_ST_SEG_PLAN, s2_);  // planning: cost scan, cuts
+    if (nseg > 1) {
         double *const wTH = j.wM + (j.wcap - 2 * (size_t)thcap), *const wIX = wTH + thcap;
         // (every thread owns a copy of the context: a wave points its own at the segment it has taken)
         for (int sgi = wave_; wave_ < ww && sgi < nseg;) {
@@ -2770,21 +2713,12 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
             int pm0 = -1;
             double lastg0 = 0;
             if (sgi > 0) pm0 = (int)f[p0 - 1], lastg0 = m[p0 - 1];
-#ifdef EGDST_STAMPS
-            const unsigned long long sgt0_ = wall_clock64();
-#endif
+            EG_STAMP_CLOCK(seg, sgt0_);
             env_walk_wave(e, j.npts, p0, p1, sgi > 0 ? 1 : 0, pm0, lastg0);
-#ifdef EGDST_STAMPS
-            if (lane_ == 0 && j.dbg) {  // diagnostic: longest segment (slot 0) and sum over segments (slot 1, was: classification)
-                const unsigned long long d_ = wall_clock64() - sgt0_;
-#if !defined(EGDST_STAMPS2) && !defined(EGDST_STAMPS5)
-                atomicMax((unsigned long long *)j.dbg + 0, d_);
-#endif
-#ifndef EGDST_STAMPS2_WHY
-                atomicAdd((unsigned long long *)j.dbg + 1, d_);
-#endif
-            }
-#endif
+            EG_STAMP_DECL(unsigned long long sgd_ = 0;)  // this segment: into the sum over the segments, and the longest one
+            EG_STAMP_TICK(seg, sgd_, sgt0_);
+            EG_STAMP_ADD(seg, lane_ == 0, j.stp, EG_ST_SEG_SUM, sgd_);
+            EG_STAMP_MAX(seg, lane_ == 0, j.stp, EG_ST_SEG_LONGEST, sgd_);
             int nx = 0;
             if (lane_ == 0) {
                 sg_oi[sgi] = e.oi, sg_oj[sgi] = e.oj, sg_err[sgi] = e.err, sg_pm[sgi] = e.pm;
@@ -2794,7 +2728,7 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
             }
             sgi = __shfl(nx, 0);
         }
-        STAMP2(4);  // the segments (wall: the longest one)
+        EG_STAMP_BLOCK(seg, j.stp, EG_ST_SEG_WALL, s2_);  // the segments (wall: the longest one)
         __syncthreads();
         if (tid_ == 0) {  // do the predictions hold?
             int ok = 1, toi = 0, toj = 0;
@@ -2850,7 +2784,7 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
                 j.oth[r] = wTH[(size_t)k * thstride + q];
                 j.oix[r] = wIX[(size_t)k * thstride + q];
             }
-            STAMP2(7);  // check + gather
+            EG_STAMP_BLOCK(seg, j.stp, EG_ST_SEG_GATHER, s2_);  // check + gather
             if (ENV_CDEFER(L)) {  // the consumption of the rows the batches kept (env_walk_wave), over the gathered rows
                 __syncthreads();
                 int k = 0, offk = 0;
@@ -2913,17 +2847,13 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
                 if (dst[u] >= 0) j.oc[dst[u]] = cc[u];
         }
     }
-#ifdef EGDST_STAMPS2
-    __syncthreads();
-    if (tid_ == 0 && j.dbg) {  // diagnostic: walks by one wave -- ticks, (<<40) how many, (<<52) how many of them not for being short
-        const int why = j.klog ? 1 : !j.wM ? 2 : ww < 2 ? 3 : j.npts < 2 * ENV_SEG_MINPTS ? 4 :
-                        (2 * (long long)j.npts + 128 + 2 * (long long)j.nthrhmax + 2 > (long long)j.wcap) ? 5 : 6;
-        atomicAdd((unsigned long long *)j.dbg + 0, (wall_clock64() - s2_) + (1ull << 40) + ((unsigned long long)(why != 4) << 52));
-#ifdef EGDST_STAMPS2_WHY  // (slot 1 then holds the reasons, 10 bits each, instead of the segments' sum)
-        atomicAdd((unsigned long long *)j.dbg + 1, 1ull << (10 * (why - 1)));
-#endif
-    }
-#endif
+    // walks by one wave: ticks, how many, and the reasons (10 bits each: kink log, no scratch, too few waves, short list,
+    // scratch too small, other)
+    EG_STAMP_DECL(const int why = j.klog ? 1 : !j.wM ? 2 : ww < 2 ? 3 : j.npts < 2 * ENV_SEG_MINPTS ? 4 :
+                                  (2 * (long long)j.npts + 128 + 2 * (long long)j.nthrhmax + 2 > (long long)j.wcap) ? 5 : 6;)
+    EG_STAMP_BLOCK(seg, j.stp, EG_ST_SEG_ONEWAVE, s2_);
+    EG_STAMP_ADD(seg, tid_ == 0, j.stp, EG_ST_SEG_NONEWAVE, 1);
+    EG_STAMP_ADD(seg, tid_ == 0, j.stp, EG_ST_SEG_WHY, 1ull << (10 * (why - 1)));
 }
 
 // lcap: sorted points that fit the dynamic LDS (32 B each: sorted M/C/V, class word, 16-bit function id and position).
@@ -2940,18 +2870,11 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
 //       and their secondary envelopes as workgroups of their own, one per (cell, choice) -- they are independent of each
 //       other (egdst_solver.c:668: envelope2 per id) -- and then the primary envelope per cell.  The lists of part 1 live in
 //       per-choice slices of the cell's work arrays; what part 2 needs besides them is handed over in Batch.sec*.
-#ifdef ENV_VGPR  // experiment: fewer registers, so that waves of the grid kernels fit next to an envelope workgroup
-#define ENV_VGPR_ATTR __attribute__((amdgpu_waves_per_eu(ENV_VGPR, ENV_VGPR)))
-#else
-#define ENV_VGPR_ATTR
-#endif
 // bxi: the workgroup's job -- cell slot of the group (part 0, 2) or cell slot * MS_ND + choice (part 1)
 static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int terminal, int lcap, int pass, int part, int bxi)
 {
     EG_DYN_LDS(dynlds);
-#ifdef EGDST_STAMPS5  // diagnostic: residency of the whole workgroup (slot 0), completed cells only
-    const unsigned long long wg_t0_ = wall_clock64();
-#endif
+    EG_STAMP_CLOCK(wg, wg_t0_);  // residency of the whole workgroup, completed cells only
     __shared__ int sh[ENV_MAXBS + 2];  // (+2: blk_reduce3 of a one-thread harness build)
     __shared__ int s_fstart[ENV_SMALLF], s_fdims[ENV_SMALLF], s_fcur[ENV_SMALLF], s_fmark[ENV_SMALLF];
     __shared__ int s_stack[2 * (ENV_SMALLF + 2)];
@@ -3052,6 +2975,7 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
     job.evfa0 = (const eg_ldsd *)s_evfa0;
     job.stack = (eg_ldsi *)s_stack;
     job.dbg = b.dbg + 16 * draw;
+    EG_STAMP_DECL(job.stp = b.stamps + (size_t)EG_NSTAMP * draw;)
     job.noseg = b.noseg;
     job.sh = sh;
     job.segstat = b.segstat + 2 * (size_t)draw;
@@ -3063,19 +2987,7 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
         if (tid == 0) *job.kcnt = 0;
     }
 
-#ifdef EGDST_STAMPS  // diagnostic build: where does a workgroup spend its time (wall_clock64 ticks of 10 ns)
-#define STAMP(k)                                                                                   \
-    do {                                                                                           \
-        if (tid == 0) {                                                                            \
-            const unsigned long long now_ = wall_clock64();                                        \
-            atomicAdd((unsigned long long *)(b.dbg + 16 * draw) + 2 + (k), now_ - stamp_);        \
-            stamp_ = now_;                                                                         \
-        }                                                                                          \
-    } while (0)
-    unsigned long long stamp_ = wall_clock64();
-#else
-#define STAMP(k)
-#endif
+    EG_STAMP_CLOCK(env, stamp_);  // where does a workgroup spend its time
     if (tid == 0) s_err = 0, s_oob = 0;
     __syncthreads();
     int any = 0, nall = 0, outn = 0, outm = 0, done = 0;
@@ -3212,7 +3124,7 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
                 if (n12 & 2) evfa0 = -INFINITY;
             }
             __syncthreads();
-            STAMP(0);  // stop rule + compaction
+            EG_STAMP_LANE(env, tid == 0, job.stp, EG_ST_ENV_STOP, stamp_);  // stop rule + compaction
             if (s_oob) ENV_FAIL(part == 1 ? -1 : (compact ? EGDST_E_CAPACITY : 2705));  // (-1: see part 2)
             // ---- does the list fold back?  then it needs a secondary envelope (:776-913) -----------
             int nfold = 0;
@@ -3353,8 +3265,8 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
         int fused = 0;
         if (job.npts <= lcap) {
             const eg_ldss *posl = blk_sort_lds(job.npts, job.nf, iM, iC, iV, iF, fstart, fdims, R1, R2, R3, Lf, Lr, lcap,
-                                               sh, &s_oob, Lq, &fused, ana, job.dbg);
-            STAMP(3);  // LDS sort
+                                               sh, &s_oob, Lq, &fused, ana, job.dbg EG_STAMP_ARG(job.stp));
+            EG_STAMP_LANE(env, tid == 0, job.stp, EG_ST_ENV_SORT, stamp_);  // LDS sort
 #ifdef EGDST_CENSUS
             cz_sort1_ = wall_clock64();
 #endif
@@ -3376,7 +3288,7 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
             return;
         } else {
             int *gcls = b.gcls + wo;  // class words of the sorted stream
-            blk_rank_sort(job.npts, job.nf, iM, iC, iV, iF, fstart, fdims, qM, qC, qV, qF, rank, sh, &s_oob, job.dbg, gcls, &fused,
+            blk_rank_sort(job.npts, job.nf, iM, iC, iV, iF, fstart, fdims, qM, qC, qV, qF, rank, sh, &s_oob, job.dbg EG_STAMP_ARG(job.stp), gcls, &fused,
                           ana, R1,
 #ifdef EGDST_EMU
                           lcap);      // (the harness keeps poisoned gaps between the LDS regions: the keys stay in the first)
@@ -3396,7 +3308,7 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
             }
         }
         __syncthreads();
-        STAMP(4);  // walk
+        EG_STAMP_LANE(env, tid == 0, job.stp, EG_ST_ENV_WALK, stamp_);  // walk
 #ifdef EGDST_CENSUS
         // (d: why << 24 | bad << 20 | sort time in us)
         if (tid == 0) EG_CENSUS(1, draw, it, jb, job.npts, job.nf | ((job.npts <= lcap ? 0 : 1) << 16),
@@ -3455,9 +3367,7 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
 #ifdef EGDST_CENSUS
         EG_CENSUS(2, draw, it, outn, outm, 0, cz_why_, wall_clock64() - cz_cell0_);
 #endif
-#ifdef EGDST_STAMPS5
-        atomicAdd((unsigned long long *)(b.dbg + 16 * draw) + 0, wall_clock64() - wg_t0_);
-#endif
+        EG_STAMP_LANE(wg, true, job.stp, EG_ST_WG_RESIDENT, wg_t0_);
         {   // algorithmic bytes of this cell: its rows written once (M, C, V; A = M - C is derived on export) and,
             // for the EGM periods, the next-period table of the same state index read once
             unsigned long long by = 24ull * (unsigned long long)(outn + 1) + 16ull * (unsigned long long)outm;
@@ -3475,7 +3385,7 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
 // kernel -- `list` holds their slots, *cnt how many; a small grid loops over them, so that a period with no such cell costs
 // a handful of workgroups that return at once instead of one 125-KB-LDS workgroup per cell of the group.  They take the
 // list's entries by ticket (eg_take_ticket; `ticket` is read in pass 3 only).
-__global__ void __launch_bounds__(ENV_MAXBS, ENV_MINW) ENV_VGPR_ATTR k_envelope(const Batch *bp_, int it, int terminal, int lcap, int pass, int part,
+__global__ void __launch_bounds__(ENV_MAXBS, ENV_MINW) k_envelope(const Batch *bp_, int it, int terminal, int lcap, int pass, int part,
                                                                                 const int *list, const int *cnt, int *ticket)
 {
     BatchRef b = EG_BATCH_REF(bp_);
@@ -3858,9 +3768,8 @@ static __device__ __forceinline__ void tp_sort(BatchRef b, int it, int stage, in
             if (threadIdx.x == 0) b.defer[cell] = 0;
         }
     }
-#ifdef EGDST_TPSTAMPS
-    const unsigned long long tpk_t0_ = wall_clock64();
-#endif
+    EG_STAMP_CLOCK(tpsort, tpk_t0_);
+    EG_STAMP_DECL(unsigned long long tpk_d_ = 0;)  // (ticks since the kernel's start: the prologue, then the whole kernel)
     TpRec *R = b.tprec + cell * MS_ND + id;
     ms_env E = eg_env(b, draw);
     const size_t Wcell = (size_t)(MS_ND + 1) * b.g.Cp;
@@ -3927,9 +3836,8 @@ static __device__ __forceinline__ void tp_sort(BatchRef b, int it, int stage, in
         iM = pM, iC = pC, iV = pV, iF = pF;
     }
     __syncthreads();
-#ifdef EGDST_TPSTAMPS
-    if (tid == 0) atomicAdd((unsigned long long *)(b.dbg + 16 * draw) + 6, wall_clock64() - tpk_t0_);
-#endif
+    EG_STAMP_TICK(tpsort, tpk_d_, tpk_t0_);
+    EG_STAMP_ADD(tpsort, tid == 0, b.stamps + (size_t)EG_NSTAMP * draw, EG_ST_TPS_PROLOGUE, tpk_d_);
     const int sec_id_ = sec_id;
     const double sec_ev_ = sec_ev;
     auto ana = [&](int g, double x) -> double {  // value of function g before its first point (env_analytic / env_evf)
@@ -3958,12 +3866,11 @@ static __device__ __forceinline__ void tp_sort(BatchRef b, int it, int stage, in
     eg_ldsi *lcls = (eg_ldsi *)(lkeys + lkcap);
     eg_ldss *lperm = (eg_ldss *)(lcls + lkcap);
 #endif
-    blk_rank_sort(npts, nf, iM, iC, iV, iF, fstart, fdims, qM, qC, qV, qF, rank, sh, &s_oob, b.dbg + 16 * draw, gcls, &fused, ana,
+    blk_rank_sort(npts, nf, iM, iC, iV, iF, fstart, fdims, qM, qC, qV, qF, rank, sh, &s_oob, b.dbg + 16 * draw EG_STAMP_ARG(b.stamps + (size_t)EG_NSTAMP * draw), gcls, &fused, ana,
                   lkeys, lkcap, lperm, lcls, lpcap);
     __syncthreads();
-#ifdef EGDST_TPSTAMPS
-    if (tid == 0) atomicAdd((unsigned long long *)(b.dbg + 16 * draw) + 7, wall_clock64() - tpk_t0_);
-#endif
+    EG_STAMP_TICK(tpsort, tpk_d_, tpk_t0_);
+    EG_STAMP_ADD(tpsort, tid == 0, b.stamps + (size_t)EG_NSTAMP * draw, EG_ST_TPS_KERNEL, tpk_d_);
     if (s_oob) TP_DEFER(10);
     if (tid == 0) {
         if (stage == 0)
@@ -3997,10 +3904,6 @@ __global__ void __launch_bounds__(TP_SORT_BS, TP_SORT_MINW) k_tp_sort(const Batc
     } while (0)
 // dynlds: the sorted stream: lcap entries of M, V (8 B), class word (4 B), function id and position list (2 B).  Any number
 // of waves: all of them load the stream and classify where the sort did not, wave 0 walks.
-// GLOBAL: the stream stays in global memory (long streams: C5's 65 536 points, C3's 12 000): the walk k_envelope runs on such
-// streams, but as a kernel of its own -- a few KB of LDS and 168 VGPRs, so that several cells share a CU where k_envelope, sized
-// for its LDS-resident streams, takes a CU per cell.
-template <bool GLOBAL>
 static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, int *list, int *cnt, int lcap, int bxi, TpShared *S, double *dynlds,
                                                int big = 0)
 {
@@ -4022,13 +3925,9 @@ static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, in
     }
     TpRec *R = b.tprec + cell * MS_ND + id;
     if (stage == 0 && (!R->active || R->nfold <= 0)) return;
-#ifdef EGDST_TPSTAMPS_WALK  // diagnostic: dbg as 8 x u64 per draw: stage*3 + {0 set-up and load, 1 the walk, 2 the rest}; 6, 7: walks per stage
-    unsigned long long tw_t_ = wall_clock64();
-#define TWST(k) do { if (tid == 0) { const unsigned long long n_ = wall_clock64(); atomicAdd((unsigned long long *)(b.dbg + 16 * draw) + stage * 3 + (k), n_ - tw_t_); tw_t_ = n_; } } while (0)
-    if (tid == 0) atomicAdd((unsigned long long *)(b.dbg + 16 * draw) + 6 + stage, 1ull);
-#else
-#define TWST(k)
-#endif
+    EG_STAMP_CLOCK(tpwalk, tw_t_);  // per stage: set-up and load, the walk, the rest; walks
+    EG_STAMP_DECL(unsigned long long *const tw_p_ = b.stamps + (size_t)EG_NSTAMP * draw + (stage ? EG_ST_TPW_LOAD1 - EG_ST_TPW_LOAD0 : 0);)
+    EG_STAMP_ADD(tpwalk, tid == 0, b.stamps + (size_t)EG_NSTAMP * draw, stage ? EG_ST_TPW_N1 : EG_ST_TPW_N0, 1);
     ms_env E = eg_env(b, draw);
     const int slot = (b.g.nslots == 2) ? (it & 1) : it;
     const size_t tk = ((size_t)slot * b.g.ndraw + draw) * MS_NST + ist;
@@ -4048,6 +3947,7 @@ static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, in
     job.evfa0 = (const eg_ldsd *)s_evfa0;
     job.stack = (eg_ldsi *)s_stack;
     job.dbg = b.dbg + 16 * draw;
+    EG_STAMP_DECL(job.stp = b.stamps + (size_t)EG_NSTAMP * draw;)
     job.noseg = b.noseg;
     job.sh = sh;
     job.segstat = b.segstat + 2 * (size_t)draw;
@@ -4104,10 +4004,6 @@ static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, in
     if (tid == 0) cz_sh_fb = 0;
     __syncthreads();
 #endif
-    if (GLOBAL) {
-        TWST(0);
-        run_walk<0, true>(&E, job, b.qM + wo, b.qC + wo, b.qV + wo, b.qF + wo, b.rank + wo, b.gcls + wo, &we, &wn, &wm, classified);
-    } else {
     if (job.npts > lcap || job.npts >= 65536) {
         if (stage == 1) TP_DEFER_LISTED(12);
         TP_DEFER(12);
@@ -4147,10 +4043,9 @@ static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, in
         }
     }
     __syncthreads();
-    TWST(0);
-    run_walk<2, true>(&E, job, Lm, b.qC + wo, Lv, Lf, Lp, Lc, &we, &wn, &wm, classified);
-    }
-    TWST(1);
+    EG_STAMP_LANE(tpwalk, tid == 0, tw_p_, EG_ST_TPW_LOAD0, tw_t_);
+    run_walk<2>(&E, job, Lm, b.qC + wo, Lv, Lf, Lp, Lc, &we, &wn, &wm, classified);
+    EG_STAMP_LANE(tpwalk, tid == 0, tw_p_, EG_ST_TPW_WALK0, tw_t_);
 #ifdef EGDST_CENSUS
     if (tid == 0) EG_CENSUS(6, draw, it, stage | (big << 4), job.npts, job.nf | (cz_sh_fb << 16), wn, wall_clock64() - cz_w0_);
 #endif
@@ -4164,7 +4059,7 @@ static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, in
 #endif
         if (we || wn >= b.g.ngridmax) TP_DEFER(13);  // (:884)
         if (tid == 0) R->cnt = wn;
-        TWST(2);
+        EG_STAMP_LANE(tpwalk, tid == 0, tw_p_, EG_ST_TPW_REST0, tw_t_);
         return;
     }
 #ifdef EGDST_CENSUS
@@ -4185,7 +4080,7 @@ static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, in
         b.tthlen[tk] = outm;
         if (evals) atomicAdd(&b.evals[draw], evals);
         atomicAdd(&b.tpstat[2 * draw], 1u);
-        TWST(2);
+        EG_STAMP_LANE(tpwalk, tid == 0, tw_p_, EG_ST_TPW_REST0, tw_t_);
         unsigned long long by = 24ull * (unsigned long long)(outn + 1) + 16ull * (unsigned long long)outm;  // (see k_envelope)
         const int slot1 = (b.g.nslots == 2) ? ((it + 1) & 1) : (it + 1);
         const size_t k1 = ((size_t)slot1 * b.g.ndraw + draw) * MS_NST + ist;
@@ -4197,7 +4092,7 @@ __global__ void __launch_bounds__(TP_WALK_BS, TP_WALK_MINW) k_tp_walk(const Batc
 {
     EG_DYN_LDS(dynlds);
     __shared__ TpShared S;
-    tp_walk<false>(EG_BATCH_REF(bp_), it, stage, list, cnt, lcap, (int)blockIdx.x, &S, (double *)dynlds);
+    tp_walk(EG_BATCH_REF(bp_), it, stage, list, cnt, lcap, (int)blockIdx.x, &S, (double *)dynlds);
 }
 // The second tier of stage 1 in ONE launch: a workgroup sorts a listed cell's lists and walks them (the sort's 12 B per point,
 // then the walk's 24 B per point, in the same dynamic LDS).  Two launches -- k_tp_sort_big, then a walk kernel -- put two more
@@ -4215,7 +4110,7 @@ __global__ void __launch_bounds__(TP_SORT_BS, TP_WALK_MINW) k_tp_big(const Batch
         tp_sort(EG_BATCH_REF(bp_), it, 1, cap, cap, biglist[k], &S, (double *)dynlds, 1);
         __threadfence_block();  // (the sorted stream goes through global memory from one phase to the next)
         __syncthreads();
-        tp_walk<false>(EG_BATCH_REF(bp_), it, 1, list, cnt, cap, biglist[k], &S, (double *)dynlds, 1);
+        tp_walk(EG_BATCH_REF(bp_), it, 1, list, cnt, cap, biglist[k], &S, (double *)dynlds, 1);
         __syncthreads();  // (the LDS of the cell is reused by the next one)
     }
 }

@@ -36,7 +36,7 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_uniform', 'egdst_set_dbgout', 'egdst_get_dbgout', 'egdst_get_walk_stats',
                'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_group_profile',
                'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys', 'egdst_simulate_batch_spec_lag',
-               'egdst_simulate_batch_spec_cov', 'egdst_cov_parts']
+               'egdst_simulate_batch_spec_cov', 'egdst_cov_parts', 'egdst_stamp_names', 'egdst_get_stamps']
 
 
 class EgdstRuntimeError(RuntimeError):
@@ -112,6 +112,8 @@ class ModelLibrary:
         L.egdst_simulate_moments.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
                                              C.c_longlong, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.egdst_get_debug.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.egdst_stamp_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
+        L.egdst_get_stamps.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]
         L.egdst_objective_dev.argtypes = [C.c_void_p, C.c_void_p]
         L.egdst_set_profile.argtypes = [C.c_void_p, C.c_int]
         L.egdst_get_profile.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
@@ -493,6 +495,17 @@ class Solver:
         out = np.zeros(16, dtype=np.int32)
         self.lib.check(self.lib.lib.egdst_get_debug(self.h, draw, _ip(out)))
         return out
+
+    def stamps(self, draw=0):
+        """{slot name: ticks of 10 ns, or a count} of one draw in the last solve; needs a library built with -DEGDST_STAMPS=<set>
+        (the slots of the other sets are zero; egdst_stamp_names, egdst_get_stamps)"""
+        L = self.lib.lib
+        n = L.egdst_stamp_names(None, 0)
+        names = (C.c_char_p * n)()
+        L.egdst_stamp_names(names, n)
+        out = np.zeros(n, dtype=np.uint64)
+        self.lib.check(L.egdst_get_stamps(self.h, draw, out.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return {names[i].decode(): int(out[i]) for i in range(n)}
 
     def cell_M(self, draw, it, ist):
         if len(self._redo) and self._route(draw)[0] is not self:

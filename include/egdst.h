@@ -336,6 +336,13 @@ int egdst_get_group_profile(egdst_handle *h, int max_groups, double *out_ms, dou
 /* Diagnostics of a tripped internal guard (EGDST_E_INTERNAL and 27xx codes): 16 ints, meaning is internal. */
 int egdst_get_debug(egdst_handle *h, int draw, int *out16);
 
+/* Clock stamps of a diagnostic build, -DEGDST_STAMPS=<set>: where the kernels of the set spend their time.
+ * egdst_stamp_names: the names of the slots, "<set>.<what>", into names[0 .. cap) (may be NULL); returns their number, the same
+ * in every build.  egdst_get_stamps: the slots of one draw as the last solve left them, that many values -- ticks of 10 ns, or
+ * counts; the slots of the sets that are not compiled in are zero.  A library built without stamps returns EGDST_E_ARG. */
+int egdst_stamp_names(const char **names, int cap);
+int egdst_get_stamps(egdst_handle *h, int draw, unsigned long long *out);
+
 /* Third output of the solver gateway, [M,D,dbgout] = egdst_solver(model) (egdst_solver.c:178-181, filled in thresholds()
  * :1866-1879, DEBUGOUT is always on in the reference): one row per kink the secondary and primary envelopes record, in the
  * order they are recorded -- it, ist, the choice whose secondary envelope it is (-1: primary), the threshold, consumption

@@ -125,6 +125,18 @@ static inline int atomicMin(int *p, int v)
     return o;
 }
 static inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { return __sync_fetch_and_add(p, v); }
+static inline unsigned long long atomicMax(unsigned long long *p, unsigned long long v)
+{
+    unsigned long long o = *p;
+    while (v > o && !__sync_bool_compare_and_swap(p, o, v)) o = *p;
+    return o;
+}
+// the clock of the stamp builds (-DEGDST_STAMPS=<set>): a count of its own reads, so that every stamp taken is a positive number
+static inline unsigned long long wall_clock64()
+{
+    static unsigned long long t;
+    return __sync_add_and_fetch(&t, 1);
+}
 
 typedef int hipError_t;
 typedef void *hipStream_t;
