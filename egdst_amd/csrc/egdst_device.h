@@ -134,7 +134,7 @@ struct Batch {
     int *negflag;        // [(draw*MS_NST+ist)*MS_ND+id] a grid point of the stream signalled c1<=0 (set by k_grid)
     int *fixn;           // [MAX_GROUPS * nt] streams listed for k_fixup per (group, period)
     int *fixlist;        // [ndraw*MS_NST*MS_ND] the lists, a group's at its first slot
-    int *tickets;        // [3][MAX_GROUPS * nt] next entry to take of a (group, period)'s k_fixup, k_envelope pass 3 and k_tp_big list (eg_take_ticket)
+    int *tickets;        // [2][MAX_GROUPS * nt] next entry to take of a (group, period)'s k_fixup list and of its k_tp_tail lists (eg_take_ticket)
     unsigned *work;      // [ndraw] re-basing calls of the draw's guess streams in this solve (straggler detection)
     int sorted_valid;    // != 0: k_sortcheck runs before the kernels of every period and stamps tsorted[cell] with sorted_valid + it
                          // when the next-period table of the cell is NOT in order (eg_tab_sorted); the base differs from solve to solve
@@ -169,7 +169,8 @@ struct Batch {
     struct TpCell *tpcell;              // [ndraw*MS_NST]
     unsigned *tpstat;                   // [2*ndraw] cells of the draw the throughput path completed / left to k_envelope, this solve
     int *tpn, *tplist;                  // [MAX_GROUPS * nt] cells per (group, period) left to k_envelope; [ndraw*MS_NST] their slots, a group's at its first
-    int *tpbign, *tpbiglist;            // the same for the cells of the second tier of stage 1 (lists beyond the regular stream budget, k_tp_*_big)
+    int *tpbign, *tpbiglist;            // the same for the cells of the second tier of stage 1 (lists beyond the regular stream budget; k_tp_tail does both lists)
+    unsigned *tpinplace;                // [ndraw] second-tier cells of the draw that gave up and were done in place by k_tp_tail, this solve
     // status
     int *status;          // [ndraw] first error code
     int *where;           // [2*ndraw] (it, ist) of that error

@@ -16,17 +16,17 @@ struct Env1Tile { unsigned long long desc, evals; };
 #endif
 #define EG_GRID_SAMPLED_ROWS 2048  // LDS rows of k_grid_lds' sampled index (tables too long to stage whole)
 #define EG_NPROF 9      // kernel classes of egdst_get_profile
-// The list-driven launches of a period (k_fixup, k_tp_big, k_envelope pass 3): workgroups per EG_SPARSE_REF_CELLS cells of the
+// The list-driven launches of a period (k_fixup, k_tp_tail): workgroups per EG_SPARSE_REF_CELLS cells of the
 // group, never fewer than that many and never more than the cap (LaunchPlan, eg_sparse_grid).  The numbers per 256 cells are what
 // was tuned with 16 groups of 256 draws of C2 (one cell per draw); a group of 1024 to 2048 draws has lists four to eight times as long.
 #define EG_SPARSE_REF_CELLS 256
 #define EG_FIX_GRID 32  // k_fixup; its workgroups take the streams k_fixup_scan listed by ticket
 #define EG_FIX_GRID_MAX 512       // (two workgroups per CU, FIX_MINW)
 #define EG_ENV_TP_MIN_CELLS 512   // (draw, state) cells per solve from which the throughput path of the envelope step is used
-#define EG_ENV_TP_REST_GRID 32    // the k_envelope launch that does the cells the throughput path left over (pass 3)
-#define EG_ENV_TP_BIG_GRID 64     // the second-tier launch of stage 1 (k_tp_big)
-#define EG_ENV_TP_GRID_MAX 256    // (both hold most of a CU's LDS: one workgroup per CU)
-// -DEG_SPARSE_GRID_MAX=n (checking builds): at most n workgroups for each of the three, so that a test's lists are many times
+#define EG_ENV_TP_REST_GRID 32    // k_tp_tail: for the cells the throughput path left over ...
+#define EG_ENV_TP_BIG_GRID 64     // ... and for the second tier of stage 1; the launch has the larger of the two,
+#define EG_ENV_TP_GRID_MAX 256    // at most this many (a workgroup holds most of a CU's LDS: one per CU)
+// -DEG_SPARSE_GRID_MAX=n (checking builds): at most n workgroups for each of them, so that a test's lists are many times
 // longer than its launches are wide.  Default: no cap.
 #define EG_ENV_TP_MAX_KEYS 5120   // points of a stream that the kernels of the throughput path keep in LDS (k_tp_walk: 24 B each)
 #ifndef EG_TP_WALK_BS0
@@ -55,9 +55,9 @@ struct LaunchPlan {
     bool env_parts;      // several choices: per-choice workgroups of k_envelope (off while the kink log is on)
     bool env_tp;         // several choices: the throughput path of the envelope step (off while the kink log is on)
     int tp_lkcap, tp_lkcap0, tp_scap0, tp_scap1, tp_bigcap;  // stream budgets of the throughput path's kernels
-    bool tp_big;         // second tier of stage 1 (k_tp_big)
+    bool tp_big;         // second tier of stage 1 (k_tp_tail's second list)
     int tp_walk_bs0;     // threads of a stage-0 walk workgroup
-    int fix_wg, tp_big_wg, tp_rest_wg;              // workgroups per EG_SPARSE_REF_CELLS cells of a group: k_fixup, k_tp_big, k_envelope pass 3
+    int fix_wg, tp_big_wg, tp_rest_wg;              // workgroups per EG_SPARSE_REF_CELLS cells of a group: k_fixup, and k_tp_tail's for its second tier and for its leftover cells
     int fix_wg_max, tp_big_wg_max, tp_rest_wg_max;  // and the most of each (eg_sparse_grid)
 };
 struct egdst_handle {
@@ -92,6 +92,7 @@ struct egdst_handle {
     int profile;                    // record HIP events around every launch of each kernel
     int lcap;                       // sorted points that fit k_envelope's dynamic LDS
     size_t lds_bytes;
+    size_t tail_lds, tail_soff;     // k_tp_tail: its dynamic LDS, and where in it the second tier's TpShared lives
     Options opt;                    // environment switches, read at create
     LaunchPlan plan;                // launch decisions of a solve, made at create
     hipEvent_t *ev;                 // [groups][EG_NPROF kernel classes][nt][2]
@@ -353,6 +354,15 @@ static unsigned eg_sparse_grid(unsigned cells, unsigned entries, int per_ref, in
     return n < entries ? n : entries;
 }
 
+#if MS_ND > 1
+static size_t tp_sort_lds(int cap)  // keys, class words, and the permutation at the next power of two (k_tp_sort)
+{
+    int p2 = 1;
+    while (p2 < cap) p2 <<= 1;
+    return (size_t)12 * cap + (size_t)2 * p2 + 64;
+}
+#endif
+
 // Regular groups of a handle.  Group 0 runs on the handle's stream and every other group on a stream of its own.  The runtime gives
 // a stream a hardware queue of its own while it has made fewer than GPU_MAX_HW_QUEUES of them; a stream that comes after that shares
 // a queue with an earlier one, which one is not ours to say, and the null stream has a queue in nearly every process (hipMemcpy uses
@@ -466,7 +476,7 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
         {(void **)&b.order, sizeof(int) * ndraw}, {(void **)&b.work, sizeof(unsigned) * ndraw},
         {(void **)&b.nregen, sizeof(unsigned) * ndraw},
         {(void **)&b.fixn, sizeof(int) * EGDST_MAX_GROUPS * g.nt}, {(void **)&b.fixlist, sizeof(int) * nds * MS_ND},
-        {(void **)&b.tickets, sizeof(int) * 3 * EGDST_MAX_GROUPS * g.nt},
+        {(void **)&b.tickets, sizeof(int) * 2 * EGDST_MAX_GROUPS * g.nt},
         {(void **)&b.negflag, sizeof(int) * nds * MS_ND}, {(void **)&b.tsorted, sizeof(int) * nds},
         {(void **)&b.secn, sizeof(int) * nds * MS_ND}, {(void **)&b.secact, sizeof(int) * nds * MS_ND},
         {(void **)&b.secerr, sizeof(int) * nds * MS_ND}, {(void **)&b.secev, sizeof(double) * nds * MS_ND},
@@ -474,7 +484,7 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
         {(void **)&b.tprec, sizeof(TpRec) * nds * MS_ND}, {(void **)&b.tpcell, sizeof(TpCell) * nds},
         {(void **)&b.tpn, sizeof(int) * EGDST_MAX_GROUPS * g.nt}, {(void **)&b.tplist, sizeof(int) * nds},
         {(void **)&b.tpbign, sizeof(int) * EGDST_MAX_GROUPS * g.nt}, {(void **)&b.tpbiglist, sizeof(int) * nds},
-        {(void **)&b.tpstat, sizeof(unsigned) * 2 * ndraw},
+        {(void **)&b.tpstat, sizeof(unsigned) * 2 * ndraw}, {(void **)&b.tpinplace, sizeof(unsigned) * ndraw},
         EG_STAMP_DECL({(void **)&b.stamps, sizeof(unsigned long long) * EG_NSTAMP * ndraw},)
 #if MS_ND == 1
         {(void **)&b.e1tiles, sizeof(Env1Tile) * nds * EG_E1_NB(d->ngridm)}, {(void **)&b.e1done, sizeof(unsigned) * nds},
@@ -530,10 +540,38 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
         // the kernels of the throughput path may ask for more than the default 64 KB of dynamic LDS (a constant per kernel)
         HIPCHK_H(hipFuncSetAttribute((const void *)k_tp_sort, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * EG_ENV_TP_MAX_KEYS + 2 * 8192 + 64));
         HIPCHK_H(hipFuncSetAttribute((const void *)k_tp_walk, hipFuncAttributeMaxDynamicSharedMemorySize, EG_TP_WALK_LDS_PER_POINT * EG_ENV_TP_MAX_KEYS));
-        HIPCHK_H(hipFuncSetAttribute((const void *)k_tp_big, hipFuncAttributeMaxDynamicSharedMemorySize, EG_TP_WALK_LDS_PER_POINT * EG_ENV_TP_MAX_KEYS));
 #endif
 #else
         if (h->lcap > 20480 * 8 / 32) h->lcap = 20480 * 8 / 32;  // the harness' static stand-in for the dynamic LDS
+#endif
+#if MS_ND > 1
+        {   // k_tp_tail: the leftover cells get k_envelope's lcap and LDS, the second tier its streams (sort, then walk, in the
+            // same bytes) and, past them, its TpShared.  The kernel's static LDS is k_envelope's and a few hundred bytes of the
+            // second tier's helpers (its TpShared is in here); lcap is passed on as it is and the sum is checked, because an
+            // lcap cut to fit would be silent and slow.
+            const LaunchPlan &p = h->plan;
+            const size_t walk_lds = (size_t)EG_TP_WALK_LDS_PER_POINT * p.tp_bigcap;
+            const size_t big_lds = !p.tp_big ? 0 : (tp_sort_lds(p.tp_bigcap) > walk_lds ? tp_sort_lds(p.tp_bigcap) : walk_lds);
+            h->tail_soff = (big_lds + 15) / 16 * 16;
+            h->tail_lds = h->tail_soff + sizeof(TpShared) > h->lds_bytes ? h->tail_soff + sizeof(TpShared) : h->lds_bytes;
+#ifndef EGDST_EMU
+            hipFuncAttributes fa, fe;
+            HIPCHK_H(hipFuncGetAttributes(&fa, (const void *)k_tp_tail));
+            HIPCHK_H(hipFuncGetAttributes(&fe, (const void *)k_envelope));
+            const size_t cu_lds = (size_t)160 * 1024;
+            if (p.env_tp && fa.sharedSizeBytes + h->tail_lds > cu_lds) {
+                egdst_destroy(h);
+                return set_err(EGDST_E_HIP, "k_tp_tail: %zu B static (k_envelope: %zu) + %zu B dynamic LDS (lcap %d, second tier %zu) exceed %zu",
+                               (size_t)fa.sharedSizeBytes, (size_t)fe.sharedSizeBytes, h->tail_lds, h->lcap, big_lds, cu_lds);
+            }
+            HIPCHK_H(hipFuncSetAttribute((const void *)k_tp_tail, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(cu_lds - fa.sharedSizeBytes)));
+#else
+            if (p.env_tp && h->tail_soff + (size_t)64 * 8 > sizeof(double) * (20480 + 64)) {  // (the stand-in, with the poisoned gaps of the second tier's regions)
+                egdst_destroy(h);
+                return set_err(EGDST_E_ARG, "k_tp_tail: the second tier's %zu B exceed the harness' stand-in for the dynamic LDS", h->tail_soff);
+            }
+#endif
+        }
 #endif
     }
 #ifndef EGDST_EMU
@@ -806,7 +844,7 @@ static int batch_for_call(egdst_handle *h, const Batch **out)
     return 0;
 }
 
-// The ticket of a list-driven launch (eg_take_ticket): which = 0 k_fixup, 1 k_envelope pass 3, 2 k_tp_big.
+// The ticket of a list-driven launch (eg_take_ticket): which = 0 k_fixup, 1 k_tp_tail.
 static int *eg_ticket(const Batch &b, int which, int gi, int it) { return b.tickets + ((size_t)which * EGDST_MAX_GROUPS + gi) * b.g.nt + it; }
 
 // One group's launches of one period: its stream, its device copy of the Batch and its range of the schedule.
@@ -819,7 +857,8 @@ struct GroupStep {
 };
 
 // profiling: class k in {0 probe/terminal, 1 the grid kernel, 2 k_envelope, 3 regeneration (k_fixup_scan + k_fixup), and the
-// kernels of the envelope step's throughput path: 4 k_tp_prep, 5 / 6 k_tp_sort stage 0 / 1, 7 / 8 k_tp_walk stage 0 / 1};
+// kernels of the envelope step's throughput path: 4 k_tp_prep, 5 / 6 k_tp_sort stage 0 / 1, 7 / 8 k_tp_walk stage 0 / 1; its tail
+// launch, k_tp_tail, is class 2};
 // events on the stream the kernels are launched on, [groups][EG_NPROF][nt][before, end]
 // (events are created when first recorded: a handle uses a fraction of the groups x classes x periods x 2 slots, and the
 //  runtime's pool of timed events is finite -- 46 080 of them at once failed with "invalid resource handle")
@@ -860,15 +899,6 @@ static void enqueue_grid(const GroupStep &s, int combos)
     //  lane per point, C4 x 32 52.6 against 51.5, C5 x 128 3.72 s either way: 133 VGPRs, three waves per SIMD instead of six to eight.)
 }
 
-#if MS_ND > 1
-static size_t tp_sort_lds(int cap)  // keys, class words, and the permutation at the next power of two (k_tp_sort)
-{
-    int p2 = 1;
-    while (p2 < cap) p2 <<= 1;
-    return (size_t)12 * cap + (size_t)2 * p2 + 64;
-}
-#endif
-
 // The envelope step of one group and period (terminal: the last period).  env_tp / env_parts: the plan's choices, off while
 // the kink log is on.  Profiling class 2, or on the throughput path its kernels one by one.
 static void enqueue_envelope(const GroupStep &s, int terminal, bool env_tp, bool env_parts)
@@ -895,7 +925,7 @@ static void enqueue_envelope(const GroupStep &s, int terminal, bool env_tp, bool
     if (env_tp && !terminal) {
         int *tcnt = b.tpn + (size_t)s.gi * b.g.nt + it, *tlist = b.tplist + (size_t)s.draw0 * MS_NST;
         int *bigc = b.tpbign + (size_t)s.gi * b.g.nt + it, *bigl = b.tpbiglist + (size_t)s.draw0 * MS_NST;
-        int *rest_tk = eg_ticket(b, 1, s.gi, it), *big_tk = eg_ticket(b, 2, s.gi, it);
+        int *tail_tk = eg_ticket(b, 1, s.gi, it);
         eg_before(s, 4);
         hipLaunchKernelGGL(k_tp_prep, dim3(nc * MS_ND), dim3(TP_BS), 0, s.gs, s.bg, it);
         eg_end(s, 4);
@@ -914,18 +944,21 @@ static void enqueue_envelope(const GroupStep &s, int terminal, bool env_tp, bool
         eg_before(s, 8);
         hipLaunchKernelGGL(k_tp_walk, dim3(nc), dim3(TP_WALK_BS), (size_t)EG_TP_WALK_LDS_PER_POINT * p.tp_lkcap, s.gs, s.bg, it, 1, tlist, tcnt,
                            p.tp_lkcap);
-        if (p.tp_big) {
-            const unsigned ng = eg_sparse_grid(nc, nc, p.tp_big_wg, p.tp_big_wg_max);
-            const size_t walk_lds = (size_t)EG_TP_WALK_LDS_PER_POINT * p.tp_bigcap;
-            const size_t lds = tp_sort_lds(p.tp_bigcap) > walk_lds ? tp_sort_lds(p.tp_bigcap) : walk_lds;
-            hipLaunchKernelGGL(k_tp_big, dim3(ng), dim3(TP_SORT_BS), lds, s.gs, s.bg, it, tlist, tcnt, p.tp_bigcap, (const int *)bigl,
-                               (const int *)bigc, big_tk);
-        }
         eg_end(s, 8);
         eg_before(s, 2);
-        // (after k_tp_big, which appends the cells it gives up on to this launch's list)
-        hipLaunchKernelGGL(k_envelope, dim3(eg_sparse_grid(nc, nc, p.tp_rest_wg, p.tp_rest_wg_max)), dim3(ENV_MAXBS), h->lds_bytes, s.gs, s.bg, it,
-                           terminal, h->lcap, 3, 0, (const int *)tlist, (const int *)tcnt, rest_tk);
+        // The tail of the period, one launch: the cells stage 1 left over (tlist, final after k_tp_walk) and its second tier (bigl,
+        // final after k_tp_sort) behind one ticket, the slow leftover cells first; a second-tier cell that gives up is done in place.
+        // Workgroups: the larger of what the two launches it replaces had (a workgroup holds most of a CU's LDS, so at most one per
+        // CU either way).  A 1365-draw group: 256 whichever way; 16 groups of 256 draws: 64, measured against their sum, 96 -- ahead
+        // in every pair of runs, by less than the runs' range (profiles/r08_tp_tail_C2_ndraw4096.txt).
+        {
+            unsigned ng = eg_sparse_grid(nc, nc, p.tp_rest_wg, p.tp_rest_wg_max);
+            const unsigned ngb = p.tp_big ? eg_sparse_grid(nc, nc, p.tp_big_wg, p.tp_big_wg_max) : 0u;
+            if (ngb > ng) ng = ngb;
+            hipLaunchKernelGGL(k_tp_tail, dim3(ng), dim3(ENV_MAXBS), h->tail_lds, s.gs, s.bg, it, h->lcap, (const int *)tlist, (const int *)tcnt,
+                               p.tp_bigcap, p.tp_big ? (const int *)bigl : (const int *)nullptr, p.tp_big ? (const int *)bigc : (const int *)nullptr,
+                               tail_tk, (int)h->tail_soff, terminal, 1, 0);
+        }
         eg_end(s, 2);
         return;
     }
@@ -974,8 +1007,9 @@ static int enqueue_solve(egdst_handle *h)
     HIPCHK(hipMemsetAsync(b.fixn, 0, sizeof(int) * EGDST_MAX_GROUPS * g.nt, s));
     HIPCHK(hipMemsetAsync(b.tpn, 0, sizeof(int) * EGDST_MAX_GROUPS * g.nt, s));
     HIPCHK(hipMemsetAsync(b.tpbign, 0, sizeof(int) * EGDST_MAX_GROUPS * g.nt, s));
-    HIPCHK(hipMemsetAsync(b.tickets, 0, sizeof(int) * 3 * EGDST_MAX_GROUPS * g.nt, s));
+    HIPCHK(hipMemsetAsync(b.tickets, 0, sizeof(int) * 2 * EGDST_MAX_GROUPS * g.nt, s));
     HIPCHK(hipMemsetAsync(b.tpstat, 0, sizeof(unsigned) * 2 * g.ndraw, s));
+    HIPCHK(hipMemsetAsync(b.tpinplace, 0, sizeof(unsigned) * g.ndraw, s));
 #if MS_ND == 1
     // k_env1: descriptors carry the period as their tag, valid within one solve; the counters count on from zero
     HIPCHK(hipMemsetAsync(b.e1tiles, 0, sizeof(Env1Tile) * (size_t)g.ndraw * MS_NST * EG_E1_NB(g.ngridm), s));
@@ -2031,6 +2065,24 @@ extern "C" int egdst_get_dbgout(egdst_handle *h, int draw, double *out, int *nro
         }
     free(rows);
     if (nrows) *nrows = n;
+    return 0;
+}
+
+extern "C" int egdst_get_tp_inplace(egdst_handle *h, unsigned *out)
+{
+    if (!h || !out) return set_err(EGDST_E_ARG, "egdst_get_tp_inplace: bad arguments");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, h->b.tpinplace, sizeof(unsigned) * h->b.g.ndraw, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int egdst_get_tp_tail_counts(egdst_handle *h, int max_groups, int *rest, int *big)
+{
+    if (!h || !rest || !big || max_groups < 1) return set_err(EGDST_E_ARG, "egdst_get_tp_tail_counts: bad arguments");
+    const size_t n = (size_t)(max_groups < EGDST_MAX_GROUPS ? max_groups : EGDST_MAX_GROUPS) * h->b.g.nt;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(rest, h->b.tpn, sizeof(int) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(big, h->b.tpbign, sizeof(int) * n, hipMemcpyDeviceToHost));
     return 0;
 }
 

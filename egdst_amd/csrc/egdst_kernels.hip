@@ -1090,7 +1090,7 @@ __global__ void __launch_bounds__(WAVE) k_fixup_scan(const Batch *bp_, int it, i
 #ifndef FIX_MINW
 #define FIX_MINW 2  // two workgroups per CU (<= 256 VGPRs); (3: at most 168 VGPRs, a k_fixup wave beside two waves of the -DENV_MINW=3 k_envelope)
 #endif
-// The list-driven launches (k_fixup, k_tp_big, k_envelope pass 3): a workgroup takes its next list entry from the launch's
+// The list-driven launches (k_fixup, k_tp_tail): a workgroup takes its next list entry from the launch's
 // ticket (one per (group, period) and kernel, beside the list's counter and cleared with it once per solve) instead of striding
 // by gridDim.x, so a slow entry holds up the workgroup that has it and nothing else.  The entries are independent and the lists'
 // order is whatever eg_list_push made it, so nothing depends on who takes which.  `sh`: one int of LDS; both barriers are
@@ -3381,10 +3381,10 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
     }
 }
 
-// pass 0 / 1 / 2: one workgroup per job of the launch.  pass 3: the cells the throughput path (k_tp_*, below) left to this
-// kernel -- `list` holds their slots, *cnt how many; a small grid loops over them, so that a period with no such cell costs
-// a handful of workgroups that return at once instead of one 125-KB-LDS workgroup per cell of the group.  They take the
-// list's entries by ticket (eg_take_ticket; `ticket` is read in pass 3 only).
+// pass 0 / 1 / 2: one workgroup per job of the launch.  pass 3: a list-driven form -- `list` holds cell slots, *cnt how many, a
+// small grid takes them by ticket (eg_take_ticket; `ticket` is read in pass 3 only).  It did the cells the throughput path left
+// over until k_tp_tail (below) took them; the host no longer launches it.  Like pass 0 its branch and arguments stay only because
+// this kernel's register allocation is not to move: passes 1 and 2 are what every other launch of the envelope step runs.
 __global__ void __launch_bounds__(ENV_MAXBS, ENV_MINW) k_envelope(const Batch *bp_, int it, int terminal, int lcap, int pass, int part,
                                                                                 const int *list, const int *cnt, int *ticket)
 {
@@ -3891,13 +3891,14 @@ __global__ void __launch_bounds__(TP_SORT_BS, TP_SORT_MINW) k_tp_sort(const Batc
 #ifndef TP_WALK_MINW
 #define TP_WALK_MINW 3  // (at most 168 VGPRs: three 4-wave workgroups per CU, what the LDS of the stream allows anyway; 172 without)
 #endif
-// stage 1 also lists the cells that are left to k_envelope (`list`, `cnt`: this (group, period)'s; every cell's stage-1
-// workgroup runs exactly once, so a cell is listed exactly once whichever kernel flagged it).
+// stage 1 also lists the cells that are left to the envelope code (`list`, `cnt`: this (group, period)'s; every cell's stage-1
+// workgroup runs exactly once, so a cell is listed exactly once whichever kernel flagged it).  The second tier (k_tp_tail) passes
+// no list: the launch that reads the list is its own, so the workgroup that holds the cell does it there and then.
 #define TP_DEFER_LISTED(why)                                                \
     do {                                                                    \
         if (threadIdx.x == 0) {                                             \
             b.defer[cell] = (why);                                           \
-            eg_list_push(b, list, cnt, b.gdraws * MS_NST, bx_, draw, it, ist); \
+            if (list) eg_list_push(b, list, cnt, b.gdraws * MS_NST, bx_, draw, it, ist); \
             atomicAdd(&b.tpstat[2 * draw + 1], 1u);                         \
         }                                                                   \
         return;                                                             \
@@ -3919,7 +3920,10 @@ static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, in
         const int df = TP_DEFERRED_UNIFORM(S, cell);
         if (df == TP_BIG && !big) return;  // the second tier of the stage decides about this cell (and lists it if it gives up)
         if (df) {
-            if (stage == 1 && tid == 0) eg_list_push(b, list, cnt, b.gdraws * MS_NST, bx_, draw, it, ist), atomicAdd(&b.tpstat[2 * draw + 1], 1u);
+            if (stage == 1 && tid == 0) {
+                if (list) eg_list_push(b, list, cnt, b.gdraws * MS_NST, bx_, draw, it, ist);
+                atomicAdd(&b.tpstat[2 * draw + 1], 1u);
+            }
             return;
         }
     }
@@ -4094,23 +4098,64 @@ __global__ void __launch_bounds__(TP_WALK_BS, TP_WALK_MINW) k_tp_walk(const Batc
     __shared__ TpShared S;
     tp_walk(EG_BATCH_REF(bp_), it, stage, list, cnt, lcap, (int)blockIdx.x, &S, (double *)dynlds);
 }
-// The second tier of stage 1 in ONE launch: a workgroup sorts a listed cell's lists and walks them (the sort's 12 B per point,
-// then the walk's 24 B per point, in the same dynamic LDS).  Two launches -- k_tp_sort_big, then a walk kernel -- put two more
-// kernel latencies and launch gaps, ~110 us, on every group's chain every period for a handful of cells (tests/diag/gpu_group_finish.py).
-// TP_SORT_BS threads: the sort's size; the walk loads with all of them and walks with up to four waves as it does elsewhere.
-__global__ void __launch_bounds__(TP_SORT_BS, TP_WALK_MINW) k_tp_big(const Batch *bp_, int it, int *list, int *cnt, int cap, const int *biglist,
-                                                                     const int *bigcnt, int *ticket)
+// The TAIL of a period's envelope step, ONE list-driven launch: the cells the throughput path left over (`restlist`, filled by
+// stage-1 k_tp_walk: eg_envelope_cell from the untouched candidates, hundreds of microseconds each) and the second tier of stage 1
+// (`biglist`, filled by stage-1 k_tp_sort: a workgroup sorts a listed cell's lists and walks them with the large stream budget --
+// the sort's 12 B per point, then the walk's 24 B per point, in the same dynamic LDS -- ~100 us each).  As two launches on one
+// stream (k_tp_big, then k_envelope pass 3) the second tier's ~210 us stood on every group's chain every period although both
+// together occupy a few dozen CUs; as one launch it runs beside the slowest leftover cell.
+//  * Both lists are FINAL when the launch starts: the counts are read once and one ticket range runs over their concatenation,
+//    the leftover cells first (a launch lasts as long as its last-started slow entry).  Nothing is appended to either list here.
+//  * A second-tier cell that gives up (tp_sort / tp_walk with big = 1 set b.defer[cell] and count it in tpstat as before) is done
+//    by the workgroup that holds it, right there: eg_envelope_cell, pass 1, as k_envelope's pass 3 would have.  b.tpinplace
+//    counts these hand-overs per draw.
+//  * The workgroup is k_envelope's (ENV_MAXBS threads, its register budget, its static LDS); TpShared lives in the dynamic LDS
+//    at byte `s_off`, past what the second tier's streams need and inside what eg_envelope_cell lays out anew for its own cell,
+//    so the static LDS is k_envelope's plus the few hundred bytes the second tier's helpers declare for themselves, and the
+//    leftover cells keep k_envelope's lcap (the host checks that the sum fits a CU).
+//  * terminal, pass, part (always 0, 1, 0) are kernel arguments, as they are k_envelope's, and not constants: with the constants
+//    folded in, the C2 batch build spilled 672 VGPRs (1216 B of scratch) against 282 (628 B; k_envelope: 253, 480 B) and the
+//    leftover cells, which set the launch's length, ran a tenth slower than in k_envelope (profiles/r08_*).
+// -DEG_TP_TAIL_GIVEUP_EVERY=n (checking builds): every n-th second-tier entry gives up before it touches anything.
+static_assert(TP_SORT_BS == ENV_MAXBS, "k_tp_tail runs the second tier's sort in k_envelope's workgroup");
+__global__ void __launch_bounds__(ENV_MAXBS, ENV_MINW) k_tp_tail(const Batch *bp_, int it, int lcap, const int *restlist, const int *restcnt,
+                                                                  int bigcap, const int *biglist, const int *bigcnt, int *ticket, int s_off, int terminal, int pass, int part)
 {
     EG_DYN_LDS(dynlds);
-    __shared__ TpShared S;
+    BatchRef b = EG_BATCH_REF(bp_);
     __shared__ int tk;
-    const int n = min(*bigcnt, EG_BATCH_REF(bp_).gdraws * MS_NST);
-    if (n <= 0) return;  // (an empty list: no ticket drawn)
+#ifdef EGDST_EMU
+    __shared__ TpShared S_;  // (the harness' stand-in for the dynamic LDS is a static array per function: nothing to share)
+    TpShared *const S = &S_;
+    (void)s_off;
+#else
+    TpShared *const S = (TpShared *)((char *)dynlds + s_off);
+#endif
+    const int cells = b.gdraws * MS_NST;
+    const int nrest = min(*restcnt, cells), nbig = biglist ? min(*bigcnt, cells) : 0;
+    const int n = nrest + nbig;
+    if (n <= 0) return;  // (both lists empty: no ticket drawn)
     for (int k; (k = eg_take_ticket(ticket, &tk)) < n;) {
-        tp_sort(EG_BATCH_REF(bp_), it, 1, cap, cap, biglist[k], &S, (double *)dynlds, 1);
-        __threadfence_block();  // (the sorted stream goes through global memory from one phase to the next)
-        __syncthreads();
-        tp_walk(EG_BATCH_REF(bp_), it, 1, list, cnt, cap, biglist[k], &S, (double *)dynlds, 1);
+        const int bx_ = (k < nrest) ? restlist[k] : biglist[k - nrest];
+        int envelope = k < nrest;
+        if (__builtin_expect(!envelope, 0)) {  // (the leftover cells' code is the one to keep in registers)
+            const int draw = b.order[b.draw0 + bx_ / MS_NST];
+            const size_t cell = (size_t)draw * MS_NST + bx_ % MS_NST;
+#ifdef EG_TP_TAIL_GIVEUP_EVERY
+            if ((k - nrest) % (EG_TP_TAIL_GIVEUP_EVERY) == 0) {
+                if (threadIdx.x == 0) b.defer[cell] = 15, atomicAdd(&b.tpstat[2 * draw + 1], 1u);
+            } else
+#endif
+            {
+                tp_sort(b, it, 1, bigcap, bigcap, bx_, S, (double *)dynlds, 1);
+                __threadfence_block();  // (the sorted stream goes through global memory from one phase to the next)
+                __syncthreads();
+                tp_walk(b, it, 1, (int *)nullptr, (int *)nullptr, bigcap, bx_, S, (double *)dynlds, 1);
+            }
+            envelope = TP_DEFERRED_UNIFORM(S, cell) != 0;  // gave up: the flag is set, the cell counted as left over
+            if (envelope && threadIdx.x == 0) atomicAdd(&b.tpinplace[draw], 1u);
+        }
+        if (envelope) eg_envelope_cell(b, it, terminal, lcap, pass, part, bx_);
         __syncthreads();  // (the LDS of the cell is reused by the next one)
     }
 }

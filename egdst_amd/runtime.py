@@ -34,7 +34,7 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_create_compact', 'egdst_geometry', 'egdst_set_groups', 'egdst_set_adaptive', 'egdst_get_schedule', 'egdst_get_work', 'egdst_get_regenerations', 'egdst_call', 'egdst_simulate_moments',
                'egdst_get_checksums', 'egdst_math_eval', 'egdst_get_evals_credited', 'egdst_simulate_batch_moments',
                'egdst_uniform', 'egdst_set_dbgout', 'egdst_get_dbgout', 'egdst_get_walk_stats',
-               'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_group_profile',
+               'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_tp_inplace', 'egdst_get_tp_tail_counts', 'egdst_get_group_profile',
                'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys', 'egdst_simulate_batch_spec_lag',
                'egdst_simulate_batch_spec_cov', 'egdst_cov_parts', 'egdst_stamp_names', 'egdst_get_stamps']
 
@@ -276,6 +276,21 @@ class Solver:
         out = np.zeros((self.ndraw, 2), dtype=np.uint32)
         self.lib.check(self.lib.lib.egdst_get_tp_stats(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def tp_inplace(self):
+        """[ndraw]: second-tier cells of the last solve that gave up and were done in place by the tail launch (egdst_get_tp_inplace)"""
+        out = np.zeros(self.ndraw, dtype=np.uint32)
+        self.lib.check(self.lib.lib.egdst_get_tp_inplace(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    MAX_GROUPS = 32   # EGDST_MAX_GROUPS of the library (egdst_set_groups: at most 32)
+
+    def tp_tail_counts(self):
+        """(rest[MAX_GROUPS, nt], big[MAX_GROUPS, nt]): per draw group and period of the last solve, the cells the throughput path left over and the
+        cells of its second tier -- the two lists of the period's tail launch (egdst_get_tp_tail_counts)"""
+        rest, big = np.zeros((self.MAX_GROUPS, self.nt), dtype=np.int32), np.zeros((self.MAX_GROUPS, self.nt), dtype=np.int32)
+        self.lib.check(self.lib.lib.egdst_get_tp_tail_counts(self.h, self.MAX_GROUPS, rest.ctypes.data_as(C.c_void_p), big.ctypes.data_as(C.c_void_p)))
+        return rest, big
 
     def work(self):
         """re-basing calls per draw in the last solve (egdst_get_work)"""

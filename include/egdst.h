@@ -322,7 +322,7 @@ int egdst_get_objective(egdst_handle *h, double *out /* host, [2*ndraw] */);
  *   0 k_probe / k_terminal      1 the grid kernel alone (k_grid_lds, k_grid_wide or k_grid)      2 k_envelope
  *   3 regeneration of guess streams (k_fixup_scan + k_fixup)
  *   4 k_tp_prep   5, 6 k_tp_sort stage 0, 1   7, 8 k_tp_walk stage 0, 1   (the envelope step's throughput path; with it on,
- *     class 2 is the k_envelope launch for the cells the path left over)
+ *     class 2 is the period's tail launch, k_tp_tail: the cells the path left over and the second tier of its stage 1)
  * the summed device time in ms and the number of bracketed launches of the LAST solve (kernels of a class that was not
  * launched: 0), and the algorithmic table bytes of that solve summed over draws (24 B per table row read once per period,
  * 24 B per row written, 16 B per threshold). */
@@ -383,6 +383,12 @@ int egdst_get_walk_stats(egdst_handle *h, unsigned *out /* [2*ndraw] */);
  * solve overrides), out[2*draw+1] = cells it left to the general kernel (an error condition, more than 64 monotone pieces
  * in a choice list, a failed draw, an infeasible state).  Results are the same either way. */
 int egdst_get_tp_stats(egdst_handle *h, unsigned *out /* [2*ndraw] */);
+/* Of the cells the throughput path left over (out[2*draw+1] above): those of the second tier of stage 1 (lists beyond the regular
+ * stream budget) that gave up and were done in place by the workgroup of the period's tail launch that held them. */
+int egdst_get_tp_inplace(egdst_handle *h, unsigned *out /* [ndraw] */);
+/* The two lists of every period's tail launch in the last solve, per draw group: entries of rest[g*nt + it] (cells left over) and
+ * big[g*nt + it] (second-tier cells), for the first max_groups groups (the library has at most 32). */
+int egdst_get_tp_tail_counts(egdst_handle *h, int max_groups, int *rest /* [max_groups*nt] */, int *big /* [max_groups*nt] */);
 
 /* Raw device views for callers that keep data resident (bench, estimation loops). */
 int egdst_device_tables(egdst_handle *h, int it, const double **M_dev, const double **C_dev, const double **V_dev,
