@@ -2740,11 +2740,13 @@ static __device__ __forceinline__ void run_walk(const ms_env *E, const WalkJob &
                     if (sg_pm[k] != (int)f[q] || !(sg_lastg[k] == m[q])) ok = 0;
                 }
             }
-#ifdef EGDST_EMU
-            if (getenv("EGDST_EMU_FAIL_SEG")) ok = 0;  // harness: every segmented walk is done again by one wave
-#endif
             if (sg_oj[0] <= 0) ok = 0;                             // (segment 0 must have left the first-point phase)
             if (toi >= j.ocap || toj >= j.nthrhmax) ok = 0;      // a full grid or threshold list: the sequential walk reports it
+#ifdef EG_SEG_FAIL_EVERY
+            // checking builds: the check fails for every n-th walk by its identity (period + state + choice of a secondary
+            // walk + 1, the primary's choice being -1), whatever the segments found: wave 0 walks again, counted as a fall-back
+            if ((j.it + j.ist + j.sec_id + 1) % (EG_SEG_FAIL_EVERY) == 0) ok = 0;
+#endif
             sg_n = ok ? nseg : 0;
             atomicAdd(&j.segstat[ok ? 0 : 1], 1u);
 #ifdef EGDST_CENSUS
@@ -4057,6 +4059,18 @@ static __device__ __forceinline__ void tp_walk(BatchRef b, int it, int stage, in
     if (tid == 0) S->res[0] = we, S->res[1] = wn, S->res[2] = wm;
     __syncthreads();
     we = S->res[0], wn = S->res[1], wm = S->res[2];
+#ifdef EG_TP_GIVEUP_EVERY
+    // checking builds: every n-th walk of one stage (EG_TP_GIVEUP_AT: 13 stage 0, 14 stage 1) takes that stage's exit below as if it had
+    // ended in an error -- after the walk has overwritten the cell's lists (stage 0) or written rows into the period's table and set
+    // the high-water marks to "unknown" (stage 1).  Decided from what every thread of the workgroup holds alike; no barrier follows.
+#if EG_TP_GIVEUP_AT == 13
+    if (stage == 0 && (it + ist + draw + id) % (EG_TP_GIVEUP_EVERY) == 0) we = 1;
+#elif EG_TP_GIVEUP_AT == 14
+    if (stage == 1 && (it + ist + draw) % (EG_TP_GIVEUP_EVERY) == 0) we = 1;
+#else
+#error "EG_TP_GIVEUP_EVERY needs EG_TP_GIVEUP_AT=13 (after the stage-0 walk) or 14 (after the stage-1 walk)"
+#endif
+#endif
     if (stage == 0) {
 #ifdef EGDST_CENSUS
         if ((we || wn >= b.g.ngridmax) && tid == 0) EG_CENSUS(5, draw, it, 0, we, job.npts, wn, 0);

@@ -24,6 +24,8 @@ def build(spec_dir, sanitize=True, env_bs=1, parallel_blocks=False, wave=1, fix_
     cmd = ['g++', '-x', 'c++', '-std=c++17', '-O1', '-g', '-mfma', '-ffp-contract=off', '-fPIC', '-shared',
            '-DEGDST_EMU', '-DENV_SEG_MINPTS=%d' % (4 * wave), '-DWAVE=%d' % wave, '-DGRID_BS=1', '-DENV_BS_EMU=%d' % env_bs, '-DFIX_BS=%d' % (1 if parallel_blocks else fix_waves * wave), '-pthread', '-I', HERE, '-I', spec_dir, '-I', CSRC, '-I', os.path.join(ROOT, 'include'),
            '-Wno-unused-function', os.path.join(CSRC, 'egdst_kernels.hip'), '-o', out]
+    if any(f.startswith('-DENV_SEG_MINPTS=') for f in extra):  # (the caller's value, not a second definition of the macro)
+        cmd = [c for c in cmd if not c.startswith('-DENV_SEG_MINPTS=')]
     cmd[1:1] = extra
     if seq_walk:
         cmd[1:1] = ['-DEGDST_SEQ_WALK']

@@ -778,7 +778,9 @@ def test_segmented_envelope_walks_are_used_and_exact(monkeypatch):
     """The envelope walk of a cell is cut at predictable points into one segment per wave, the predictions are checked
     and the segments merged (run_walk in egdst_kernels.hip); EGDST_NOSEG=1 keeps the one-wave walk.  Both ways equal the
     oracle bit for bit (C2 and C3 at full size: LDS-resident and global-memory streams), the statistics show that the
-    cutting really happens, and fallbacks (a failed prediction is not an error) stay rare."""
+    cutting really happens, and fallbacks (a failed prediction is not an error) stay rare -- on these models there is none, so
+    the fall-back itself (wave 0 walking the stream again after the segments have written the scratch rows) is not run here:
+    tests/test_gpu_forced_recoveries.py forces it in checking builds (-DEG_SEG_FAIL_EVERY) and holds it to the oracle."""
     for name in ('C2', 'occ3_n1400_global_path'):
         m = SCALED[name]()
         ref = Oracle(m).solve()
