@@ -34,6 +34,7 @@ struct Env1Tile { unsigned long long desc, evals; };
 #endif
 #define EG_TP_WALK_LDS_PER_POINT 24  // k_tp_walk: M, V (8 B each), class word (4 B), function id and position list (2 B each)
 #include <optional>
+#include <vector>
 // Environment switches of the library (INTEGRATION.md), read once when a handle is created: unset (nullopt) means the
 // automatic choice, a set value is taken as atoi reads it.
 struct Options {
@@ -83,6 +84,12 @@ struct egdst_handle {
     size_t sim_spec_bytes, sim_tgt_bytes, sim_W_bytes;
     double *sim_scores;         // egdst_simulate_batch_spec_cov: the per-agent scores of a slice of draws, [nd][nsim][cov_padded(nmom)]
     size_t sim_scores_bytes;
+    // egdst_policy_batch: the observations, their grouping by cell (permutation, workgroup items), and the terms of a slice of draws
+    egdst_obs *pol_obs;
+    int *pol_perm, *pol_flag;
+    PolItem *pol_items;
+    double *pol_term;
+    size_t pol_obs_bytes, pol_perm_bytes, pol_flag_bytes, pol_items_bytes, pol_term_bytes;
     size_t klog_bytes;  // kink log (egdst_set_dbgout), allocated apart from the pool
     void **emu_items;  // sanitizer harness only: one heap block per array instead of the pool
     int emu_nitems;
@@ -774,7 +781,8 @@ extern "C" int egdst_destroy(egdst_handle *h)
     if (h->b.kcnt) (void)hipFree(h->b.kcnt);
     {
         void *simbufs[] = {h->sim_init, h->sim_rs, h->sim_sims, h->sim_means, h->sim_err, h->sim_counts,
-                           h->sim_spec, h->sim_tgt, h->sim_W, h->sim_scores};
+                           h->sim_spec, h->sim_tgt, h->sim_W, h->sim_scores,
+                           h->pol_obs, h->pol_perm, h->pol_flag, h->pol_items, h->pol_term};
         for (void *p : simbufs)
             if (p) (void)hipFree(p);
     }
@@ -1700,6 +1708,104 @@ extern "C" int egdst_simulate_batch_spec_cov(egdst_handle *h, const double *init
 }
 
 extern "C" int egdst_cov_parts(void) { return COV_P; }
+
+// The policy at a data panel's observations, every draw of the handle (include/egdst.h).  Every argument is checked before
+// anything is enqueued.  The observations are grouped by cell (it, ist) once per call -- a stable permutation, cut into items of
+// at most POL_BS observations of one cell -- so that a workgroup of k_policy_obs searches one table of one draw; results go to the
+// caller's index, so the grouping shows nowhere.  With a fit asked for, the terms of a slice of draws (EG_POL_SLICE_BYTES) go to
+// scratch kept on the handle and k_policy_fit reduces them on the handle's stream before the next slice overwrites them; without,
+// no scratch is reserved and the draws go in one launch (65535 at a time: the grid's second dimension).
+#ifndef EG_POL_SLICE_BYTES
+#define EG_POL_SLICE_BYTES (1ull << 30)
+#endif
+static_assert(sizeof(egdst_obs) == 40 && offsetof(egdst_obs, cash) == 16 && offsetof(egdst_obs, w) == 32,
+              "egdst_obs is 4 ints and 3 doubles (the Python dtype mirrors it)");
+
+extern "C" int egdst_policy_parts(void) { return POL_BS; }
+
+extern "C" int egdst_policy_batch(egdst_handle *h, const egdst_obs *obs, int nobs, int resid, double *cons_dev, int *id_dev,
+                                  double *vf_dev, double *ssr_dev, int *hits_dev)
+{
+    const char *who = "egdst_policy_batch";
+    if (!h || !obs || nobs <= 0) return set_err(EGDST_E_ARG, "%s: bad arguments", who);
+#if MS_NCONT > 0
+    return set_err(EGDST_E_ARG, "%s: a model with continuous states is not served (its policy is a blend over grid corners)", who);
+#else
+    if (resid != 0 && resid != 1) return set_err(EGDST_E_ARG, "%s: resid is not 0 or 1", who);
+    if (!cons_dev && !id_dev && !vf_dev && !ssr_dev && !hits_dev) return set_err(EGDST_E_ARG, "%s: no output is given", who);
+    if (!h->keep_history) return set_err(EGDST_E_ARG, "%s: needs keep_history=1", who);
+    if (!h->solved) return set_err(EGDST_E_NOT_SOLVED, "%s", egdst_strerror(EGDST_E_NOT_SOLVED));
+    if (!h->params_set && MS_NPARAM) return set_err(EGDST_E_ARG, "%s: parameters not set", who);
+    const Geom &g = h->b.g;
+    for (int k = 0; k < nobs; k++) {
+        const egdst_obs &o = obs[k];
+        const char *bad = nullptr;
+        if (o.it < 0 || o.it >= g.nt) bad = "it is outside the model's periods";
+        else if (o.ist < 0 || o.ist >= MS_NST) bad = "ist is outside the model's states";
+        else if (o.id < -1 || o.id >= MS_ND) bad = "id is outside the model's decisions (-1: not observed)";
+        else if (o.reserved != 0) bad = "reserved is not 0";
+        else if (!(o.cash >= g.a0)) bad = "cash is NaN or below a0";   // (above mmax the policy is extrapolated, as the simulator does from its second period on)
+        else if (!(o.w >= 0.0)) bad = "w is NaN or negative";
+        else if (resid == 1 && o.cons <= 0.0) bad = "resid = 1 with a consumption that is not positive";
+        if (bad) return set_err(EGDST_E_ARG, "%s: observation %d: %s", who, k, bad);
+    }
+    // the grouping: a counting sort by cell keeps the caller's order inside a cell
+    const int ncell = g.nt * MS_NST;
+    std::vector<int> first((size_t)ncell + 1, 0), perm((size_t)nobs);
+    for (int k = 0; k < nobs; k++) first[(size_t)obs[k].it * MS_NST + obs[k].ist + 1]++;
+    for (int c = 0; c < ncell; c++) first[c + 1] += first[c];
+    {
+        std::vector<int> next(first.begin(), first.end() - 1);
+        for (int k = 0; k < nobs; k++) perm[next[(size_t)obs[k].it * MS_NST + obs[k].ist]++] = k;
+    }
+    std::vector<PolItem> items;
+    for (int c = 0; c < ncell; c++)
+        for (int f = first[c]; f < first[c + 1]; f += POL_BS) {
+            const int left = first[c + 1] - f;
+            items.push_back(PolItem{c / MS_NST, c % MS_NST, f, left < POL_BS ? left : POL_BS});
+        }
+    const bool fit = ssr_dev || hits_dev;
+    const size_t per_draw = (sizeof(double) + sizeof(int)) * (size_t)nobs;
+    int slice = fit ? (int)(EG_POL_SLICE_BYTES / per_draw) : g.ndraw;
+    if (slice > 65535) slice = 65535;
+    if (slice < 1) slice = 1;
+    if (slice > g.ndraw) slice = g.ndraw;
+    int rc = sim_reserve((void **)&h->pol_obs, &h->pol_obs_bytes, sizeof(egdst_obs) * (size_t)nobs);
+    if (!rc) rc = sim_reserve((void **)&h->pol_perm, &h->pol_perm_bytes, sizeof(int) * (size_t)nobs);
+    if (!rc) rc = sim_reserve((void **)&h->pol_items, &h->pol_items_bytes, sizeof(PolItem) * items.size());
+    if (!rc && fit) rc = sim_reserve((void **)&h->pol_term, &h->pol_term_bytes, sizeof(double) * (size_t)nobs * slice);
+    if (!rc && fit) rc = sim_reserve((void **)&h->pol_flag, &h->pol_flag_bytes, sizeof(int) * (size_t)nobs * slice);
+    if (rc) return rc;
+    hipStream_t s = h->stream;
+    const Batch *bdev = nullptr;
+    rc = batch_for_call(h, &bdev);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(h->pol_obs, obs, sizeof(egdst_obs) * (size_t)nobs, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->pol_perm, perm.data(), sizeof(int) * (size_t)nobs, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->pol_items, items.data(), sizeof(PolItem) * items.size(), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);   // (an upload may still read the vectors)
+        return set_err(EGDST_E_HIP, "%s: upload failed: %s", who, hipGetErrorString(e));
+    }
+    PolArgs a;
+    a.nobs = nobs, a.resid = resid;
+    a.obs = h->pol_obs, a.perm = h->pol_perm, a.items = h->pol_items;
+    a.cons = cons_dev, a.vf = vf_dev, a.id = id_dev;
+    a.term = fit ? h->pol_term : nullptr, a.flag = fit ? h->pol_flag : nullptr;
+    for (int d0 = 0; d0 < g.ndraw; d0 += slice) {
+        const int nd = (g.ndraw - d0 < slice) ? g.ndraw - d0 : slice;
+        a.draw0 = d0;
+        hipLaunchKernelGGL(k_policy_obs, dim3((unsigned)items.size(), nd), dim3(POL_BS), 0, s, bdev, a);
+        if (fit)
+            hipLaunchKernelGGL(k_policy_fit, dim3(nd), dim3(POL_BS), 0, s, bdev, d0, nobs, (const double *)h->pol_term,
+                               (const int *)h->pol_flag, ssr_dev, hits_dev);
+    }
+    e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(s);   // (the uploads read perm and items; the results are written on return)
+    if (e != hipSuccess || e2 != hipSuccess) return set_err(EGDST_E_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : e2));
+    return 0;
+#endif
+}
 
 // egdst_call.c:17-164.  The index checks of the gateway are done here, in row order, because an out-of-range index
 // turns the switch to -1 for the rest of the call (that row and every later one are NaN) and a wrong column count

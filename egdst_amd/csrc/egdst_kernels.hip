@@ -4508,6 +4508,26 @@ static __host__ __device__ __forceinline__ double eg_uniform(unsigned long long 
     return (double)(z >> 11) * 0x1p-53;
 }
 
+// The policy of one table at cp->cash (policy, egdst_simulator.c:145-199), for an agent standing at (cp->it, cp->ist): returns
+// consumption, sets cp->savings and cp->id (the threshold scan) and *vf, the simulator's form of the value -- u(c) + discount *
+// V[0] below M[1] when V[0] > -inf, the interpolation of V otherwise (not the accessor's three-way form, k_call).  len >= 2 is the
+// caller's check.  k_simulate and k_policy_obs share it, so the policy exists once.
+static __device__ __forceinline__ double eg_policy_at(const ms_env *E, ms_pv *cp, const double *M, const double *C, const double *V,
+                                                      const double *TH, const double *D, int len, int thlen, double *vf)
+{
+    const int i = eg_bracket(cp->cash, M, len, 0);
+    const double c = eg_lerp(cp->cash, M[i], M[i + 1], C[i], C[i + 1]);
+    cp->savings = cp->cash - c;
+    int ith = 0;
+    while (ith < thlen && cp->cash >= TH[ith]) ith++;
+    cp->id = (int)D[max(ith - 1, 0)];
+    if (cp->cash < M[1] && V[0] > -INFINITY)
+        *vf = ms_utility(E, cp, c) + ms_discount(E, cp) * V[0];
+    else
+        *vf = eg_lerp(cp->cash, M[i], M[i + 1], V[i], V[i + 1]);
+    return c;
+}
+
 __global__ void __launch_bounds__(GRID_BS) k_simulate(const Batch *bp_, SimArgs a)
 {
     BatchRef b = EG_BATCH_REF(bp_);
@@ -4654,17 +4674,8 @@ __global__ void __launch_bounds__(GRID_BS) k_simulate(const Batch *bp_, SimArgs 
             atomicCAS(a.err, 0, EGDST_E_NOT_SOLVED);
             return;
         }
-        const int i = eg_bracket(cp.cash, t.M, t.len, 0);
-        const double c = eg_lerp(cp.cash, t.M[i], t.M[i + 1], t.C[i], t.C[i + 1]);
-        cp.savings = cp.cash - c;
-        int ith = 0;
-        while (ith < t.thlen && cp.cash >= t.TH[ith]) ith++;
-        cp.id = (int)t.D[max(ith - 1, 0)];
         double vf;
-        if (cp.cash < t.M[1] && t.V[0] > -INFINITY)
-            vf = ms_utility(&E, &cp, c) + ms_discount(&E, &cp) * t.V[0];
-        else
-            vf = eg_lerp(cp.cash, t.M[i], t.M[i + 1], t.V[i], t.V[i + 1]);
+        const double c = eg_policy_at(&E, &cp, t.M, t.C, t.V, t.TH, t.D, t.len, t.thlen, &vf);
 #endif
         double *o = a.sims + ((size_t)isim * nt + it) * a.nout;
         o[0] = cp.cash;
@@ -4775,6 +4786,126 @@ __global__ void __launch_bounds__(GRID_BS) k_call(const Batch *bp_, CallArgs a)
         r = NAN;
     }
     a.res[i] = r;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The policy at a data panel's observations, every draw (egdst_policy_batch, include/egdst.h): k_policy_obs evaluates the policy,
+// one lane per (observation, draw), and k_policy_fit reduces a draw's terms in the contract's order.
+#ifdef EGDST_EMU
+#define POL_BS 1
+#else
+#define POL_BS 256
+#endif
+static_assert((POL_BS & (POL_BS - 1)) == 0, "the summation order of k_policy_fit is a tree over a power of two");
+struct PolItem {   // the share of one workgroup: `count` (<= POL_BS) entries of the permutation from `first` on, all of cell (it, ist)
+    int it, ist, first, count;
+};
+struct PolArgs {
+    int draw0, nobs, resid;    // first draw of the launch (blockIdx.y counts on from it)
+    const egdst_obs *obs;      // [nobs], the caller's order
+    const int *perm;           // [nobs] the observations grouped by cell, stable
+    const PolItem *items;      // [gridDim.x]
+    double *cons, *vf;         // the caller's [ndraw][nobs], or nullptr
+    int *id;
+    double *term;              // [draws of the launch][nobs] the terms w * (r * r), or nullptr: no fit
+    int *flag;                 // beside them: -1 no policy here (the cell is missing), else bit 0 the term counts, bit 1 a hit
+};
+
+// One lane per (observation, draw of the launch).  A workgroup serves observations of ONE cell of one draw (the host's items), so
+// the table's address, its lengths and the model's environment are uniform over the workgroup and its lanes search one column,
+// where it lies, in global memory, by the routine k_simulate uses.  Results go to the caller's index.
+__global__ void __launch_bounds__(POL_BS) k_policy_obs(const Batch *bp_, PolArgs a)
+{
+#if MS_NCONT == 0   // (continuous states: the host refuses, the policy is a blend over grid corners)
+    BatchRef b = EG_BATCH_REF(bp_);
+    const PolItem w = a.items[blockIdx.x];
+    const int draw = a.draw0 + (int)blockIdx.y;
+    if ((int)threadIdx.x >= w.count) return;
+    const int k = a.perm[w.first + threadIdx.x];
+    const egdst_obs o = a.obs[k];
+    Tab t = {};
+    if (b.status[draw] == 0) t = eg_tab(b, w.it, draw, w.ist);   // (a failed draw has no complete solution; history kept: slot = period)
+    const bool have = t.len >= 2;
+    double c = NAN, vf = NAN;
+    int id = -1;
+    if (have) {
+        ms_env E = eg_env(b, draw);
+        ms_pv cp;
+        cp.it = w.it;
+        cp.ist = w.ist;
+        cp.id = 0;
+        cp.cash = o.cash;
+        cp.savings = 0;
+        cp.shock = NAN;
+        c = eg_policy_at(&E, &cp, t.M, t.C, t.V, t.TH, t.D, t.len, t.thlen, &vf);
+        id = cp.id;
+    }
+    const size_t at = (size_t)draw * a.nobs + k;   // results at the caller's index
+    if (a.cons) a.cons[at] = c;
+    if (a.id) a.id[at] = id;
+    if (a.vf) a.vf[at] = vf;
+    if (a.term) {
+        double term = 0.0;
+        int fl = -1;
+        if (have) {
+            fl = 0;
+            if (o.cons == o.cons && o.w != 0.0) {   // (consumption observed, and weighted)
+                const double r = a.resid ? MS_LOG(o.cons) - MS_LOG(c) : o.cons - c;
+                const double r2 = r * r;
+                term = o.w * r2;
+                fl = 1;
+            }
+            if (o.id >= 0 && o.id == id) fl |= 2;
+        }
+        const size_t st = (size_t)blockIdx.y * a.nobs + k;
+        a.term[st] = term;
+        a.flag[st] = fl;
+    }
+#endif
+}
+
+// ssr and hits of one draw, one workgroup per draw of the launch, in the order of the contract (include/egdst.h): thread t adds
+// the terms of the observations k = t (mod POL_BS) in ascending k, then a fixed tree over the threads; the hits are an integer
+// count.  An observation without a policy (flag -1: its cell is missing) makes the draw's ssr NaN; a failed draw reads NaN and -1.
+__global__ void __launch_bounds__(POL_BS) k_policy_fit(const Batch *bp_, int draw0, int nobs, const double *term, const int *flag,
+                                                       double *ssr, int *hits)
+{
+    BatchRef b = EG_BATCH_REF(bp_);
+    __shared__ double ps[POL_BS];
+    __shared__ int ph[POL_BS], pbad[POL_BS];
+    const int tid = threadIdx.x, draw = draw0 + (int)blockIdx.x;
+    if (b.status[draw] != 0) {   // (the whole workgroup leaves, ahead of every barrier)
+        if (tid == 0) {
+            if (ssr) ssr[draw] = NAN;
+            if (hits) hits[draw] = -1;
+        }
+        return;
+    }
+    term += (size_t)blockIdx.x * nobs;
+    flag += (size_t)blockIdx.x * nobs;
+    double acc = 0.0;
+    int h = 0, bad = 0;
+    for (int k = tid; k < nobs; k += POL_BS) {
+        const int f = flag[k];
+        if (f < 0) {
+            bad = 1;
+            continue;
+        }
+        if (f & 1) acc += term[k];
+        h += (f >> 1) & 1;
+    }
+    ps[tid] = acc;
+    ph[tid] = h;
+    pbad[tid] = bad;
+    __syncthreads();
+    for (int o = POL_BS / 2; o > 0; o >>= 1) {
+        if (tid < o) ps[tid] += ps[tid + o], ph[tid] += ph[tid + o], pbad[tid] |= pbad[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (ssr) ssr[draw] = pbad[0] ? NAN : ps[0];
+        if (hits) hits[draw] = ph[0];
+    }
 }
 
 #ifdef EGDST_EMU

@@ -654,6 +654,19 @@ class egdstmodel:  # noqa: N801  (reference class name)
         from . import runtime
         return runtime.call_model(self, self.CALL_NAMES[func], funcargs)
 
+    def policy(self, it, ist, cash):
+        """``(c, id, vf)`` of the solved model at the points (it, ist, cash): consumption, the discrete choice and the value, as
+        the simulator computes them for an agent standing there (egdst_simulator.c:145-199; no counterpart gateway in the
+        reference).  it, ist and the returned id follow ``call``'s MATLAB conventions -- the period as the model counts it
+        (t0 .. T), state and decision 1-based -- converted here only; vector input, one row per point."""
+        if self.needtocompile or self.M is None:
+            raise EgdstError('The model needs to be compiled and solved first!\nRun <model>.compile')
+        from . import runtime
+        it0 = np.atleast_1d(np.asarray(it)).astype(np.int64) - int(self.t0)
+        ist0 = np.atleast_1d(np.asarray(ist)).astype(np.int64) - 1
+        c, idx, vf = runtime.policy_model(self, it0, ist0, cash)
+        return c, np.where(idx >= 0, idx + 1, idx), vf
+
     def sims2panel(self):
         # egdstmodel.m:1279-1292
         if self.sims is None:

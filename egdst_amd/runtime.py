@@ -36,7 +36,8 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_uniform', 'egdst_set_dbgout', 'egdst_get_dbgout', 'egdst_get_walk_stats',
                'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_tp_inplace', 'egdst_get_tp_tail_counts', 'egdst_get_group_profile',
                'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys', 'egdst_simulate_batch_spec_lag',
-               'egdst_simulate_batch_spec_cov', 'egdst_cov_parts', 'egdst_stamp_names', 'egdst_get_stamps']
+               'egdst_simulate_batch_spec_cov', 'egdst_cov_parts', 'egdst_stamp_names', 'egdst_get_stamps',
+               'egdst_policy_batch', 'egdst_policy_parts']
 
 
 class EgdstRuntimeError(RuntimeError):
@@ -94,6 +95,8 @@ class ModelLibrary:
         L.egdst_simulate_batch_spec_cov.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_longlong, C.c_ulonglong,
                                                     C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.egdst_cov_parts.argtypes = []
+        L.egdst_policy_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+        L.egdst_policy_parts.argtypes = []
         L.egdst_uniform.restype = C.c_double
         L.egdst_uniform.argtypes = [C.c_ulonglong, C.c_ulonglong]
         L.egdst_set_dbgout.argtypes = [C.c_void_p, C.c_int]
@@ -163,6 +166,12 @@ class ModelLibrary:
         """partial sums P of the covariance's summation order (the library's COV_P, egdst_cov_parts): what
         MomentSpec.covariance takes as `parts` to give the device's bits"""
         return int(self.lib.egdst_cov_parts())
+
+    @property
+    def policy_parts(self):
+        """partial sums B of the fit's summation order (the library's POL_BS, egdst_policy_parts): what datafit.fit_mirror takes
+        as `block` to give the device's bits"""
+        return int(self.lib.egdst_policy_parts())
 
     def quantile_eval(self, x, p):
         """(quantiles p of the host array x by the device's selection, the number of non-NaN values): egdst_quantile_eval,
@@ -637,6 +646,33 @@ class Solver:
         return self._estimation_step(self.lib.lib.egdst_simulate_batch_spec_cov, init, seed, rndtype, randstream_dev, nrand, (nmom,),
                                      (rec.ctypes.data_as(C.c_void_p), nmom), (nmom, nmom), means_dev, counts_dev, cov_dev)
 
+    POLICY_OUTPUTS = ('cons', 'id', 'vf', 'ssr', 'hits')
+
+    def policy_batch(self, obs, resid=0, want=POLICY_OUTPUTS, cons_dev=None, id_dev=None, vf_dev=None, ssr_dev=None, hits_dev=None):
+        """egdst_policy_batch: the policy at the observations of a data panel for every draw of THIS handle (draws redone after a
+        capacity overflow read as failed here), and the fit per draw.  obs is a datafit.Observations or an array of
+        datafit.OBS_DTYPE; resid 0: cons - c, 1: log(cons) - log(c).  Cash above mmax is NOT refused: the tables are
+        extrapolated over their last two rows, as the simulator does for an agent whose cash has grown past the grid, however far above
+        the grid the data lie -- a caller who wants such observations out of the fit gives them w = 0 or leaves them out.  The *_dev arguments are device pointers (ints); with none
+        given, the outputs named in `want` are torch device tensors allocated here and returned as a dict: cons, vf float64
+        [ndraw, nobs], id int32 [ndraw, nobs], ssr float64 [ndraw], hits int32 [ndraw]."""
+        from . import datafit
+        rec = datafit.records(obs)
+        ptr = dict(cons=cons_dev, id=id_dev, vf=vf_dev, ssr=ssr_dev, hits=hits_dev)
+        out = None
+        if all(v is None for v in ptr.values()) and len(want):   # (nothing wanted: the library refuses the call)
+            import torch
+            unknown = [k for k in want if k not in self.POLICY_OUTPUTS]
+            if unknown:
+                raise EgdstRuntimeError(1, 'policy_batch: unknown outputs %s' % unknown)
+            shape = lambda k: (self.ndraw, len(rec)) if k in ('cons', 'id', 'vf') else (self.ndraw,)   # noqa: E731
+            out = {k: torch.zeros(*shape(k), dtype=torch.int32 if k in ('id', 'hits') else torch.float64, device='cuda') for k in want}
+            torch.cuda.current_stream().synchronize()   # (torch fills on ITS stream, the library writes on the handle's)
+            ptr = {k: (out[k].data_ptr() if k in out else None) for k in self.POLICY_OUTPUTS}
+        self.lib.check(self.lib.lib.egdst_policy_batch(self.h, rec.ctypes.data_as(C.c_void_p), len(rec), int(resid),
+                                                       *[C.c_void_p(ptr[k]) if ptr[k] else None for k in self.POLICY_OUTPUTS]))
+        return out
+
     def call(self, sw, args, draw=0):
         """egdst_call gateway (egdst_call.c:17-164): sw 1 utility, 2 marginal utility, 3 discount, 4 budget, 5 marginal
         budget, 6 value function; args [narg x ncol] with 1-based it/ist/id as in MATLAB.  Returns [narg]."""
@@ -723,6 +759,16 @@ def _solver_with_solution(model):
 
 def call_model(model, sw, args):
     return _solver_with_solution(model).call(sw, args, draw=0)
+
+
+def policy_model(model, it, ist, cash):
+    """(c, id, vf) of the model's current solution at the points (it, ist, cash), it and ist 0-based: one draw through
+    egdst_policy_batch"""
+    from . import datafit
+    s = _solver_with_solution(model)
+    obs = datafit.Observations(it, ist, cash)
+    out = s.policy_batch(obs, want=('cons', 'id', 'vf'))
+    return out['cons'][0].cpu().numpy(), out['id'][0].cpu().numpy(), out['vf'][0].cpu().numpy()
 
 
 def simulate_model(model, rndtype):

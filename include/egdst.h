@@ -298,6 +298,49 @@ int egdst_simulate_batch_spec_cov(egdst_handle *h, const double *init, int nsim,
 /* The number P of partial sums of the covariance's summation order (build constant COV_P: one per wave of k_moment_cov's
  * 256-thread workgroup), a power of two in [1, 256]. */
 int egdst_cov_parts(void);
+
+/* One observation of a data panel, the other half of the estimation step (new surface): a household seen in
+ * period it (0-based model period) in state ist (0-based, as column 5 of the simulated paths) with cash-in-hand `cash`, that
+ * chose id (0-based as column 4; -1: the choice was not observed) and consumed cons (NaN: not observed), with weight w in the
+ * fit.  reserved must be 0. */
+typedef struct {
+    int it, ist, id, reserved;
+    double cash, cons, w;
+} egdst_obs;   /* 40 bytes, no padding */
+
+/* The model's policy at every observation, for EVERY draw of the handle, and per draw the fit to the observed consumption and
+ * choices: non-linear least squares, or (resid = 1) the log residuals of a likelihood with measurement error in consumption.
+ * obs is HOST memory [nobs]; the five outputs are DEVICE buffers, each may be NULL but one must be given:
+ *   cons_dev [ndraw][nobs], id_dev [ndraw][nobs], vf_dev [ndraw][nobs]   the policy at observation k of draw d, at [d*nobs + k]
+ *   ssr_dev [ndraw]    the weighted sum of squared residuals;   hits_dev [ndraw]   the correctly predicted choices
+ * Requires keep_history=1.  Runs on the handle's stream, after the solve enqueued there; returns when the results are written.
+ * Per (draw, observation) exactly what the simulator does for an agent standing at (it, ist) with `cash` (policy,
+ * egdst_simulator.c:145-199; the kernels share one routine): on the table of (it, draw, ist), i the bracket of cash in the M
+ * column (bxsearch), c the interpolation of C over rows i, i+1 (linter's expression, two divisions); id = D[max(j - 1, 0)], j the
+ * number of leading thresholds TH <= cash; vf = u(c) + discount * V[0] when cash < M[1] and V[0] > -inf, else the interpolation of
+ * V over the same rows.  (egdst_call's value function has a third branch, -inf; this is the simulator's form.)
+ * A draw that failed to solve has NaN / -1 / NaN at every observation, ssr NaN and hits -1.  In a solved draw an observation
+ * whose cell was not solved (fewer than 2 rows) has NaN / -1 / NaN and makes that draw's ssr NaN, whether or not it enters the
+ * fit; hits counts the other observations.
+ * The fit, every operation a rounded fp64 operation, no FMA: r_k = cons_k - c_k (resid 0) or log(cons_k) - log(c_k) (resid 1,
+ * the log of include/egdst_math.h: glibc's bits; a c_k <= 0 flows through as -inf / NaN); term_k = w_k * (r_k * r_k), the square
+ * rounded, then the product.  Observations with cons NaN or w == 0 are skipped.
+ * Summation order (part of the contract; B = egdst_policy_parts() = 256 in this library): partial t (0 <= t < B) starts at 0.0
+ * and adds the terms of the observations k = t (mod B) that are not skipped in ascending k; then for o = B/2 .. 1: p[t] += p[t+o]
+ * (t < o); ssr = p[0].  hits is the exact number of observations with id_k >= 0 equal to the predicted decision.  The order is
+ * over the caller's indices: the order in which the library's lanes take the observations and the slices it cuts the draws into
+ * change no bit of any result.
+ * EGDST_E_ARG before anything is launched, with the observation's index in egdst_last_error where one is at fault: nobs <= 0; it
+ * outside [0, nt) or ist outside [0, nst); id outside [-1, nd); reserved != 0; cash NaN or below a0 (above mmax the tables are
+ * extrapolated over their last two rows, as the simulator does for an agent whose cash has grown past mmax: more than half of the
+ * pairs of a simulated occ3 panel stand there); w NaN or negative; resid not 0 or 1; resid = 1 with a cons <= 0; no output given; a model with continuous
+ * states (there the simulator's policy is a blend over grid corners: not served). */
+int egdst_policy_batch(egdst_handle *h, const egdst_obs *obs /* host, [nobs] */, int nobs, int resid,
+                       double *cons_dev /* [ndraw][nobs] */, int *id_dev /* [ndraw][nobs] */, double *vf_dev /* [ndraw][nobs] */,
+                       double *ssr_dev /* [ndraw] */, int *hits_dev /* [ndraw] */);
+/* The number B of partial sums of the fit's summation order (build constant POL_BS: the threads of k_policy_fit's workgroup), a
+ * power of two. */
+int egdst_policy_parts(void);
 /* Uniform number k of stream `seed` (host replay of the device generator): with z = seed + (k+1)*0x9E3779B97F4A7C15,
  * z = (z ^ z>>30)*0xBF58476D1CE4E5B9, z = (z ^ z>>27)*0x94D049BB133111EB, z ^= z>>31 (splitmix64): (z >> 11) * 2^-53. */
 double egdst_uniform(unsigned long long seed, unsigned long long k);
