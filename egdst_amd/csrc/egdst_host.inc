@@ -84,6 +84,8 @@ struct egdst_handle {
     size_t sim_spec_bytes, sim_tgt_bytes, sim_W_bytes;
     double *sim_scores;         // egdst_simulate_batch_spec_cov: the per-agent scores of a slice of draws, [nd][nsim][cov_padded(nmom)]
     size_t sim_scores_bytes;
+    double *sim_band;           // the same entry on a spec with a banded quantile: the sparsities k_quantile_band writes, [ndraw][nmom]
+    size_t sim_band_bytes;
     // egdst_policy_batch: the observations, their grouping by cell (permutation, workgroup items), and the terms of a slice of draws
     egdst_obs *pol_obs;
     int *pol_perm, *pol_flag;
@@ -781,7 +783,7 @@ extern "C" int egdst_destroy(egdst_handle *h)
     if (h->b.kcnt) (void)hipFree(h->b.kcnt);
     {
         void *simbufs[] = {h->sim_init, h->sim_rs, h->sim_sims, h->sim_means, h->sim_err, h->sim_counts,
-                           h->sim_spec, h->sim_tgt, h->sim_W, h->sim_scores,
+                           h->sim_spec, h->sim_tgt, h->sim_W, h->sim_scores, h->sim_band,
                            h->pol_obs, h->pol_perm, h->pol_flag, h->pol_items, h->pol_term};
         for (void *p : simbufs)
             if (p) (void)hipFree(p);
@@ -1549,6 +1551,9 @@ extern "C" double egdst_uniform(unsigned long long seed, unsigned long long k) {
 // cov_dev (egdst_simulate_batch_spec_cov only; needs spec): every slice also goes through k_moment_scores and k_moment_cov, which
 // writes the slice's matrices straight into cov_dev [ndraw][nmom][nmom]; the scores of a slice then count beside its paths
 // towards EG_SIM_SLICE_BYTES.  Without cov_dev the slices, the launches and the uploads are those of the step without it.
+// With cov_dev and a quantile in the spec (it carries a bandwidth: the door checked) every slice also launches k_quantile_band
+// over the span of quantile records, between k_quantiles and k_moment_scores, into h->sim_band [ndraw][nmom], which is reserved
+// only then; a spec without one enqueues what it did.
 static int estimation_step(egdst_handle *h, const double *init, int nsim, const double *randstream_dev, long long nrand,
                            unsigned long long seed, int rndtype, const egdst_moment_lag *spec, int nmom, const double *target,
                            const double *W, double *means_dev, int *counts_dev, double *obj_dev, double *cov_dev)
@@ -1577,8 +1582,10 @@ static int estimation_step(egdst_handle *h, const double *init, int nsim, const 
     int slice = (int)(EG_SIM_SLICE_BYTES / (per_draw ? per_draw : 1));
     if (slice < 1) slice = 1;
     if (slice > g.ndraw) slice = g.ndraw;
+    const bool banded = cov_dev && q_last >= q_first;   // (the covariance door takes a quantile only with its bandwidth)
     if (cov_dev) {
         rc = sim_reserve((void **)&h->sim_scores, &h->sim_scores_bytes, score_draw * slice);
+        if (!rc && banded) rc = sim_reserve((void **)&h->sim_band, &h->sim_band_bytes, sizeof(double) * (size_t)nmom * g.ndraw);
         if (rc) return rc;
     }
     for (int d0 = 0; d0 < g.ndraw; d0 += slice) {
@@ -1592,12 +1599,16 @@ static int estimation_step(egdst_handle *h, const double *init, int nsim, const 
             hipLaunchKernelGGL(k_quantiles, dim3(q_last - q_first + 1, nd), dim3(QNT_BS), 0, h->stream, (const double *)h->sim_sims,
                                nsim, g.nt, (const egdst_moment_lag *)h->sim_spec, q_first, nmom, h->sim_means + (size_t)d0 * nmom,
                                h->sim_counts + (size_t)d0 * nmom);
+        if (banded)   // the sparsities of the banded quantiles, over the same span of records
+            hipLaunchKernelGGL(k_quantile_band, dim3(q_last - q_first + 1, nd), dim3(QNT_BS), 0, h->stream, (const double *)h->sim_sims,
+                               nsim, g.nt, (const egdst_moment_lag *)h->sim_spec, q_first, nmom, h->sim_band + (size_t)d0 * nmom,
+                               (double *)nullptr);
         if (cov_dev) {
             const int ntile = cov_padded(nmom) / COV_T;
             hipLaunchKernelGGL(k_moment_scores, dim3((unsigned)(((size_t)nsim * cov_padded(nmom) + MOM_BS - 1) / MOM_BS), nd), dim3(MOM_BS),
                                0, h->stream, (const double *)h->sim_sims, nsim, g.nt, (const egdst_moment_lag *)h->sim_spec, nmom,
                                (const double *)(h->sim_means + (size_t)d0 * nmom), (const int *)(h->sim_counts + (size_t)d0 * nmom),
-                               h->sim_scores);
+                               (const double *)(banded ? h->sim_band + (size_t)d0 * nmom : nullptr), h->sim_scores);
             hipLaunchKernelGGL(k_moment_cov, dim3(ntile * (ntile + 1) / 2, nd), dim3(COV_BS), 0, h->stream,
                                (const double *)h->sim_scores, nsim, nmom, cov_dev + (size_t)d0 * nmom * nmom);
         }
@@ -1630,10 +1641,22 @@ extern "C" int egdst_simulate_batch_moments(egdst_handle *h, const double *init,
 // The step with user-defined moments and a full weighting matrix: the objective is e' W e.  Every argument is checked before
 // anything is enqueued.  The device sees one record type, egdst_moment_lag; egdst_simulate_batch_spec promotes its
 // egdst_moment records with zero lags and `who` names the door in the messages.  cov_dev: the door is
-// egdst_simulate_batch_spec_cov, which takes no quantile.
+// egdst_simulate_batch_spec_cov, which takes a quantile only with a bandwidth (hi) that keeps p - h and p + h inside (0, 1).
 static_assert(sizeof(egdst_moment) == 56, "egdst_moment is 6 ints and 4 doubles (the Python dtype mirrors it)");
 static_assert(sizeof(egdst_moment_lag) == 64 && offsetof(egdst_moment_lag, lag2) == 56 && offsetof(egdst_moment_lag, cond_lag) == 60,
               "egdst_moment_lag is egdst_moment and 2 ints (the Python dtype mirrors it)");
+// What is wrong with bandwidth h of quantile p (0 < p < 1) for the covariance, or nullptr: the band's ends are the rounded fp64
+// difference and sum, as k_quantile_band forms them.
+static const char *qnt_band_problem(double p, double h)
+{
+    if (h == 0.0) return "a quantile has no covariance without a bandwidth (hi)";
+    if (!(h > 0.0)) return "the bandwidth of a quantile (hi) is NaN or not positive";   // (NaN fails)
+    const double lo = p - h, hi = p + h;
+    if (lo <= 0.0) return "the bandwidth of a quantile (hi) reaches p - h <= 0";
+    if (hi >= 1.0) return "the bandwidth of a quantile (hi) reaches p + h >= 1";
+    return nullptr;
+}
+
 // Do the periods [it_first, it_last] shifted by -lag stay inside [0, nt)?  (64-bit: no int lag overflows)
 static bool lag_inside(int it_first, int it_last, int lag, int nt)
 {
@@ -1650,8 +1673,8 @@ static int checked_estimation_step(const char *who, egdst_handle *h, const doubl
         const egdst_moment_lag &q = spec[j];
         const char *bad = nullptr;
         if (q.kind < 0 || q.kind > 3) bad = "kind is not 0, 1, 2 or 3";
-        else if (q.kind == 3 && cov_dev) bad = "a quantile has no covariance here";
         else if (q.kind == 3 && !(q.lo > 0.0 && q.lo < 1.0)) bad = "the p of a quantile (lo) is not inside (0, 1)";   // (NaN fails both)
+        else if (q.kind == 3 && cov_dev && qnt_band_problem(q.lo, q.hi)) bad = qnt_band_problem(q.lo, q.hi);   // (no other door reads hi)
         else if (q.col < 0 || q.col >= nout) bad = "col is outside the simulated columns";
         else if (q.col2 < 0 || q.col2 >= nout) bad = "col2 is outside the simulated columns";
         else if (q.cond_col < -1 || q.cond_col >= nout) bad = "cond_col is outside the simulated columns";
@@ -2097,6 +2120,64 @@ extern "C" int egdst_quantile_eval(int n, const double *x, int np, const double 
     if (d_cnt) (void)hipFree(d_cnt);
     free(panel), free(rec), free(cnt);
     if (e != hipSuccess) return set_err(EGDST_E_HIP, "egdst_quantile_eval: %s", hipGetErrorString(e));
+    return 0;
+}
+
+// k_quantile_band on caller-supplied values (diagnostics), the panel and the records laid out as egdst_quantile_eval does: record i
+// is quantile p[i] with bandwidth h[i]; out [np][3] receives the band's ends a, b and the sparsity s.  k_quantiles runs beside it
+// only for the count.
+extern "C" int egdst_quantile_band_eval(int n, const double *x, int np, const double *p, const double *hband, double *out, int *count)
+{
+    const char *who = "egdst_quantile_band_eval";
+    if (n < 1 || np < 1 || !x || !p || !hband || !out || !count) return set_err(EGDST_E_ARG, "%s: bad arguments", who);
+    for (int i = 0; i < np; i++) {
+        if (!(p[i] > 0.0 && p[i] < 1.0)) return set_err(EGDST_E_ARG, "%s: p[%d] is not inside (0, 1)", who, i);
+        if (qnt_band_problem(p[i], hband[i])) return set_err(EGDST_E_ARG, "%s: record %d: %s", who, i, qnt_band_problem(p[i], hband[i]));
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return set_err(EGDST_E_NOGPU, "%s", egdst_strerror(EGDST_E_NOGPU));
+    const size_t npanel = (size_t)n * EG_NOUT;
+    double *panel = (double *)malloc(sizeof(double) * npanel);
+    egdst_moment_lag *rec = (egdst_moment_lag *)calloc((size_t)np, sizeof(egdst_moment_lag));
+    double *res = (double *)malloc(sizeof(double) * 3 * (size_t)np);   // [np] sparsities, then [np][2] ends
+    int *cnt = (int *)malloc(sizeof(int) * (size_t)np);
+    double *d_panel = nullptr, *d_res = nullptr, *d_means = nullptr;
+    egdst_moment_lag *d_rec = nullptr;
+    int *d_cnt = nullptr;
+    if (!panel || !rec || !res || !cnt) {
+        free(panel), free(rec), free(res), free(cnt);
+        return set_err(EGDST_E_HIP, "%s: out of host memory", who);
+    }
+    for (size_t i = 0; i < npanel; i++) panel[i] = NAN;
+    for (int i = 0; i < n; i++) panel[(size_t)i * EG_NOUT] = x[i];
+    for (int i = 0; i < np; i++) rec[i].kind = 3, rec[i].cond_col = -1, rec[i].lo = p[i], rec[i].hi = hband[i];
+    hipError_t e = hipMalloc(&d_panel, sizeof(double) * npanel);
+    if (e == hipSuccess) e = hipMalloc(&d_rec, sizeof(egdst_moment_lag) * (size_t)np);
+    if (e == hipSuccess) e = hipMalloc(&d_res, sizeof(double) * 3 * (size_t)np);
+    if (e == hipSuccess) e = hipMalloc(&d_means, sizeof(double) * (size_t)np);
+    if (e == hipSuccess) e = hipMalloc(&d_cnt, sizeof(int) * (size_t)np);
+    if (e == hipSuccess) e = hipMemcpy(d_panel, panel, sizeof(double) * npanel, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rec, rec, sizeof(egdst_moment_lag) * (size_t)np, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_quantiles, dim3(np), dim3(QNT_BS), 0, 0, (const double *)d_panel, n, 1, (const egdst_moment_lag *)d_rec, 0, np,
+                           d_means, d_cnt);
+        hipLaunchKernelGGL(k_quantile_band, dim3(np), dim3(QNT_BS), 0, 0, (const double *)d_panel, n, 1, (const egdst_moment_lag *)d_rec, 0,
+                           np, d_res, d_res + np);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(res, d_res, sizeof(double) * 3 * (size_t)np, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(cnt, d_cnt, sizeof(int) * (size_t)np, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) {
+        for (int i = 0; i < np; i++) out[3 * i] = res[np + 2 * i], out[3 * i + 1] = res[np + 2 * i + 1], out[3 * i + 2] = res[i];
+        *count = cnt[0];   // (the records share the column and the period: one count)
+    }
+    if (d_panel) (void)hipFree(d_panel);
+    if (d_rec) (void)hipFree(d_rec);
+    if (d_res) (void)hipFree(d_res);
+    if (d_means) (void)hipFree(d_means);
+    if (d_cnt) (void)hipFree(d_cnt);
+    free(panel), free(rec), free(res), free(cnt);
+    if (e != hipSuccess) return set_err(EGDST_E_HIP, "%s: %s", who, hipGetErrorString(e));
     return 0;
 }
 

@@ -5014,32 +5014,33 @@ static __device__ __forceinline__ unsigned long long qnt_candidate(const double 
     return qnt_key(egm_bits(x));
 }
 
-// Quantile moments (kind 3 of egdst_moment_lag, include/egdst.h) of one draw's simulated paths by exact selection: one workgroup
-// per (record j0 + blockIdx.x, draw of the launch); records of another kind leave at once.  Most-significant-digit radix
-// select on the 64-bit keys: pass d counts, in a 256-bin histogram, byte 7 - d of the keys that agree with the digits
-// selected so far, the bin that holds rank k becomes the next digit and k the rank inside it; after eight passes the digits
-// are the key.  Only integers are added, so the result does not depend on scheduling.  A record with at most QNT_LDS_KEYS
-// candidates (nsim times its periods) gathers its keys into LDS once -- a column read is strided by EG_NOUT doubles -- the
-// others read the column in every pass.  Every loop with a barrier has workgroup-uniform bounds; what one thread decides
-// (n, the bin, the new k) goes through LDS and a barrier.
-__global__ void __launch_bounds__(QNT_BS) k_quantiles(const double *sims, int nsim, int nt, const egdst_moment_lag *spec, int j0,
-                                                      int nmom, double *means, int *counts)
+// Rank of quantile p among n values (include/egdst.h): the ceil of the one fp64 product, clamped to [1, n].
+static __device__ __forceinline__ unsigned qnt_rank(double p, unsigned n)
 {
-    __shared__ unsigned long long skey[QNT_LDS_KEYS];
-    __shared__ unsigned shist[256];
-    __shared__ unsigned sgrp[16];   // sums of 16 bins each
-    __shared__ unsigned ssel[3];    // selected bin, rank inside it, n
-    const int j = j0 + blockIdx.x, tid = threadIdx.x;
-    const egdst_moment_lag q = spec[j];
-    if (q.kind != 3) return;   // (the whole workgroup, ahead of every barrier)
-    const size_t per_agent = (size_t)EG_NOUT * nt;
-    sims += (size_t)blockIdx.y * per_agent * nsim;
-    means += (size_t)blockIdx.y * nmom;
-    counts += (size_t)blockIdx.y * nmom;
-    const int np = q.it_last - q.it_first + 1, ncand = nsim * np;   // (the host checked that the product fits an int)
-    const bool in_lds = ncand <= QNT_LDS_KEYS;
-    if (in_lds)
-        for (int c = tid; c < ncand; c += QNT_BS) skey[c] = qnt_candidate(sims, per_agent, q, np, c);
+    long long kk = (long long)ceil(p * (double)n);
+    kk = kk < 1 ? 1 : (kk > (long long)n ? (long long)n : kk);
+    return (unsigned)kk;
+}
+
+// The value whose key is `key` (the inverse of qnt_key).
+static __device__ __forceinline__ double qnt_value(unsigned long long key)
+{
+    return egm_from_bits((key >> 63) ? (key & ~(1ull << 63)) : ~key);
+}
+
+// The selection pass of the quantile kernels, by the whole workgroup: the key of rank qnt_rank(p, n) among the n qualifying
+// candidates of record q, n left in ssel[2] (0: nothing qualifies, and the key returned means nothing).  Most-significant-digit
+// radix select on the 64-bit keys: pass d counts, in a 256-bin histogram, byte 7 - d of the keys that agree with the digits
+// selected so far, the bin that holds rank k becomes the next digit and k the rank inside it; after eight passes the digits
+// are the key.  Only integers are added, so the result does not depend on scheduling.  in_lds: the caller gathered the keys
+// into skey (the first barrier here makes them visible); otherwise the column is read again in every pass.  Every loop with a
+// barrier has workgroup-uniform bounds; what one thread decides (n, the bin, the new k) goes through LDS and a barrier.  A
+// second call may follow at once: three barriers lie between its first write to ssel and the last read here.
+static __device__ __forceinline__ unsigned long long qnt_select(const double *sims, size_t per_agent, const egdst_moment_lag &q, int np,
+                                                                int ncand, bool in_lds, double p, const unsigned long long *skey,
+                                                                unsigned *shist, unsigned *sgrp, unsigned *ssel)
+{
+    const int tid = threadIdx.x;
     unsigned long long prefix = 0, mask = 0;   // the digits selected so far, and the bits they occupy
     for (int pass = 0; pass < 8; pass++) {
         const int shift = 56 - 8 * pass;
@@ -5061,10 +5062,8 @@ __global__ void __launch_bounds__(QNT_BS) k_quantiles(const double *sims, int ns
             if (pass == 0) {   // the histogram of the first digit holds every qualifying value: n, and from it the rank
                 unsigned n = 0;
                 for (int g = 0; g < 16; g++) n += sgrp[g];
-                long long kk = (long long)ceil(q.lo * (double)n);
-                kk = kk < 1 ? 1 : (kk > (long long)n ? (long long)n : kk);
                 ssel[2] = n;
-                k = (unsigned)kk;
+                k = qnt_rank(p, n);
             } else {
                 k = ssel[1];
             }
@@ -5090,10 +5089,76 @@ __global__ void __launch_bounds__(QNT_BS) k_quantiles(const double *sims, int ns
         mask |= 255ull << shift;
         __syncthreads();   // (ssel and the histogram are read before the next pass writes them)
     }
+    return prefix;
+}
+
+// Quantile moments (kind 3 of egdst_moment_lag, include/egdst.h) of one draw's simulated paths by exact selection (qnt_select):
+// one workgroup per (record j0 + blockIdx.x, draw of the launch); records of another kind leave at once.  A record with at most
+// QNT_LDS_KEYS candidates (nsim times its periods) gathers its keys into LDS once -- a column read is strided by EG_NOUT
+// doubles -- the others read the column in every pass.
+__global__ void __launch_bounds__(QNT_BS) k_quantiles(const double *sims, int nsim, int nt, const egdst_moment_lag *spec, int j0,
+                                                      int nmom, double *means, int *counts)
+{
+    __shared__ unsigned long long skey[QNT_LDS_KEYS];
+    __shared__ unsigned shist[256];
+    __shared__ unsigned sgrp[16];   // sums of 16 bins each
+    __shared__ unsigned ssel[3];    // selected bin, rank inside it, n
+    const int j = j0 + blockIdx.x, tid = threadIdx.x;
+    const egdst_moment_lag q = spec[j];
+    if (q.kind != 3) return;   // (the whole workgroup, ahead of every barrier)
+    const size_t per_agent = (size_t)EG_NOUT * nt;
+    sims += (size_t)blockIdx.y * per_agent * nsim;
+    means += (size_t)blockIdx.y * nmom;
+    counts += (size_t)blockIdx.y * nmom;
+    const int np = q.it_last - q.it_first + 1, ncand = nsim * np;   // (the host checked that the product fits an int)
+    const bool in_lds = ncand <= QNT_LDS_KEYS;
+    if (in_lds)
+        for (int c = tid; c < ncand; c += QNT_BS) skey[c] = qnt_candidate(sims, per_agent, q, np, c);
+    const unsigned long long key = qnt_select(sims, per_agent, q, np, ncand, in_lds, q.lo, skey, shist, sgrp, ssel);
     if (tid == 0) {
         const unsigned n = ssel[2];
         counts[j] = (int)n;
-        means[j] = n ? egm_from_bits((prefix >> 63) ? (prefix & ~(1ull << 63)) : ~prefix) : NAN;
+        means[j] = n ? qnt_value(key) : NAN;
+    }
+}
+
+// The sparsity of the banded quantiles (a kind-3 record with its bandwidth h in hi; egdst_simulate_batch_spec_cov, include/egdst.h):
+// s = (b - a) / ((double)(k_hi - k_lo) / (double)n) with a and b the order statistics of ranks k_lo = qnt_rank(p - h, n) and
+// k_hi = qnt_rank(p + h, n) among the record's n qualifying values -- the spacing estimate of 1 / f at the quantile, which
+// k_moment_scores turns into the agents' scores.  One workgroup per (record j0 + blockIdx.x, draw of the launch), records of
+// another kind leave at once; the keys are gathered once, as in k_quantiles, and qnt_select runs twice over that one gather.
+// Thread 0 writes s to band [nd][nmom] (n = 0 and k_hi == k_lo: NaN; a == b with distinct ranks: 0.0) and, where ends is given
+// (egdst_quantile_band_eval), a and b to ends [nd][nmom][2].
+__global__ void __launch_bounds__(QNT_BS) k_quantile_band(const double *sims, int nsim, int nt, const egdst_moment_lag *spec, int j0,
+                                                          int nmom, double *band, double *ends)
+{
+    __shared__ unsigned long long skey[QNT_LDS_KEYS];
+    __shared__ unsigned shist[256];
+    __shared__ unsigned sgrp[16];
+    __shared__ unsigned ssel[3];
+    const int j = j0 + blockIdx.x, tid = threadIdx.x;
+    const egdst_moment_lag q = spec[j];
+    if (q.kind != 3) return;   // (the whole workgroup, ahead of every barrier)
+    const size_t per_agent = (size_t)EG_NOUT * nt;
+    sims += (size_t)blockIdx.y * per_agent * nsim;
+    const int np = q.it_last - q.it_first + 1, ncand = nsim * np;
+    const bool in_lds = ncand <= QNT_LDS_KEYS;
+    if (in_lds)
+        for (int c = tid; c < ncand; c += QNT_BS) skey[c] = qnt_candidate(sims, per_agent, q, np, c);
+    const double p_lo = q.lo - q.hi, p_hi = q.lo + q.hi;
+    const unsigned long long key_a = qnt_select(sims, per_agent, q, np, ncand, in_lds, p_lo, skey, shist, sgrp, ssel);
+    const unsigned long long key_b = qnt_select(sims, per_agent, q, np, ncand, in_lds, p_hi, skey, shist, sgrp, ssel);
+    if (tid == 0) {
+        const unsigned n = ssel[2];
+        double a = NAN, b = NAN, s = NAN;
+        if (n) {
+            a = qnt_value(key_a), b = qnt_value(key_b);
+            const double mass = (double)(qnt_rank(p_hi, n) - qnt_rank(p_lo, n)) / (double)n;
+            s = (b - a) / mass;
+        }
+        const size_t o = (size_t)blockIdx.y * nmom + j;
+        band[o] = s;
+        if (ends) ends[2 * o] = a, ends[2 * o + 1] = b;
     }
 }
 
@@ -5164,9 +5229,11 @@ static __host__ __device__ __forceinline__ int cov_padded(int nmom) { return (nm
 // ascending period (from 0.0; kind 2 adds 1.0 or 0.0) and d = (s - m_j * c) / N_j with the mean and the count k_moments wrote:
 // one product, one difference, one quotient (an empty moment: NaN - falls out of m_j = NaN and 0 / 0).  scores [nd][nsim][nmomp],
 // the record the fastest index: the lanes of a wave read one or two agents' paths and write consecutive doubles.  Padding
-// columns j >= nmom are 0.0.  One thread per (agent, column); blockIdx.y is the draw of the launch.
+// columns j >= nmom are 0.0.  One thread per (agent, column); blockIdx.y is the draw of the launch.  A kind-3 record (a banded
+// quantile) counts instead the agent's pairs c and those of them t whose key is <= the key of the quantile k_quantiles wrote,
+// and d = (s_j * (p * c - t)) / N_j with the sparsity s_j k_quantile_band left in band [nd][nmom] (unread without such a record).
 __global__ void __launch_bounds__(MOM_BS) k_moment_scores(const double *sims, int nsim, int nt, const egdst_moment_lag *spec, int nmom,
-                                                          const double *means, const int *counts, double *scores)
+                                                          const double *means, const int *counts, const double *band, double *scores)
 {
     const int nmomp = cov_padded(nmom);
     const size_t e = (size_t)blockIdx.x * MOM_BS + threadIdx.x;
@@ -5180,6 +5247,20 @@ __global__ void __launch_bounds__(MOM_BS) k_moment_scores(const double *sims, in
     const egdst_moment_lag q = spec[j];
     const size_t per_agent = (size_t)EG_NOUT * nt;
     const double *p = sims + ((size_t)blockIdx.y * nsim + i) * per_agent;
+    if (q.kind == 3) {   // a banded quantile: d = (s_j * (p * c - t)) / N_j, t the agent's pairs at or below the quantile in key order
+        const unsigned long long key_q = qnt_key(egm_bits(means[(size_t)blockIdx.y * nmom + j]));
+        int c = 0, t = 0;
+        for (int it = q.it_first; it <= q.it_last; it++) {
+            double x;
+            if (!eg_moment_term(p + (size_t)it * EG_NOUT, q, &x)) continue;
+            c++;
+            if (qnt_key(egm_bits(x)) <= key_q) t++;
+        }
+        const double pc = q.lo * (double)c;
+        const double w = band[(size_t)blockIdx.y * nmom + j] * (pc - (double)t);
+        *out = w / (double)counts[(size_t)blockIdx.y * nmom + j];
+        return;
+    }
     double s = 0;
     int c = 0;
     for (int it = q.it_first; it <= q.it_last; it++) {

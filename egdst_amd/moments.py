@@ -6,11 +6,12 @@
     spec += [mo.median('M', periods=it) for it in range(nt)] + [mo.quantile('A', 0.9, where=('id', 1, 1))]
     means, counts, obj = solver.simulate_batch_spec(init, spec, target=t, W=W)
     data_means, data_counts = spec.evaluate(data_panel)      # the same definitions, summed in the same order, on the host
-    # the covariance of the moments (a spec without quantiles): per draw on the device, and of the data panel on the host, which
-    # is the Omega a user inverts into W
-    plain = mo.MomentSpec(spec[:-nt - 1], layout=solver.lib.info)
-    means, counts, cov = solver.simulate_batch_cov(init, plain)           # cov [ndraw, nmom, nmom]
-    data_means, data_counts, data_cov = plain.covariance(data_panel, parts=solver.lib.cov_parts)
+    # the covariance of the moments: per draw on the device, and of the data panel on the host, which is the Omega a user
+    # inverts into W.  A quantile needs a bandwidth for it (the spacing estimate of the density at the quantile)
+    h = mo.quantile_bandwidth(0.5, nsim)
+    banded = mo.MomentSpec(spec[:-nt - 1] + [mo.median('M', periods=it, bandwidth=h) for it in range(nt)], layout=solver.lib.info)
+    means, counts, cov = solver.simulate_batch_cov(init, banded)          # cov [ndraw, nmom, nmom]
+    data_means, data_counts, data_cov = banded.covariance(data_panel, parts=solver.lib.cov_parts)
 
 Columns are 0-based indices of the simulated panel (egdst_simulate, model.sims) or the tokens of the model strings:
 M C A V id ist mu sigma shock u df, then st1.. (nnst states), dc1.. (nnd decisions), eq1.. (neq equations).  `periods` is
@@ -106,14 +107,59 @@ def transition(col, frm, to, periods=None, lag=1):
     return share(col, to, periods=periods, where=(col, frm, frm, lag))
 
 
-def quantile(col, p, periods=None, where=None):
-    """quantile p (0 < p < 1) of the present values of sims[col]: the ceil(p n)-th smallest of the n, no interpolation"""
-    return Moment(QUANTILE, col, periods=periods, where=where, lo=float(p))
+def quantile(col, p, periods=None, where=None, bandwidth=None):
+    """quantile p (0 < p < 1) of the present values of sims[col]: the ceil(p n)-th smallest of the n, no interpolation.
+    bandwidth: the h of the spacing estimate of the density at the quantile (0 < p - h, p + h < 1; quantile_bandwidth gives the
+    usual choices), which the covariance needs and nothing else reads; None: the record carries none and has no covariance"""
+    return Moment(QUANTILE, col, periods=periods, where=where, lo=float(p), hi=0.0 if bandwidth is None else float(bandwidth))
 
 
-def median(col, periods=None, where=None):
+def median(col, periods=None, where=None, bandwidth=None):
     """quantile(col, 0.5): the lower middle value of an even number of values"""
-    return quantile(col, 0.5, periods=periods, where=where)
+    return quantile(col, 0.5, periods=periods, where=where, bandwidth=bandwidth)
+
+
+def bandwidth_problem(p, h):
+    """why the library refuses bandwidth h on a quantile p (the rules of egdst_simulate_batch_spec_cov, on the rounded fp64 sum and
+    difference), or None; h == 0.0 is no bandwidth at all, which only the covariance refuses"""
+    p, h = float(p), float(h)
+    if h == 0.0:
+        return None
+    if not h > 0.0:   # (NaN fails too)
+        return 'is NaN or not positive'
+    if p - h <= 0.0:
+        return 'reaches p - h <= 0'
+    if p + h >= 1.0:
+        return 'reaches p + h >= 1'
+    return None
+
+
+def quantile_bandwidth(p, n, rule='bofinger'):
+    """the usual bandwidth h of the spacing estimate for quantile p of n values: 'bofinger',
+    h = n^(-1/5) (4.5 phi(z)^4 / (2 z^2 + 1)^2)^(1/5), or 'hall-sheather',
+    h = n^(-1/3) z_0.975^(2/3) (1.5 phi(z)^2 / (2 z^2 + 1))^(1/3), with z the normal quantile of p and phi the normal density;
+    clipped to what a record accepts (p - h > 0 and p + h < 1 as rounded).  A convenience: no bit contract."""
+    from statistics import NormalDist
+    p, n = float(p), float(n)
+    if not 0.0 < p < 1.0:
+        raise ValueError('quantile_bandwidth: p = %r is outside (0, 1)' % p)
+    if not n >= 1.0:
+        raise ValueError('quantile_bandwidth: n = %r is not a number of values' % n)
+    nd = NormalDist()
+    z = nd.inv_cdf(p)
+    f = nd.pdf(z)
+    if rule == 'bofinger':
+        h = n ** -0.2 * (4.5 * f ** 4 / (2.0 * z * z + 1.0) ** 2) ** 0.2
+    elif rule == 'hall-sheather':
+        h = n ** (-1.0 / 3.0) * nd.inv_cdf(0.975) ** (2.0 / 3.0) * (1.5 * f * f / (2.0 * z * z + 1.0)) ** (1.0 / 3.0)
+    else:
+        raise ValueError('quantile_bandwidth: rule %r is neither \'bofinger\' nor \'hall-sheather\'' % (rule,))
+    h = min(h, 0.5 * min(p, 1.0 - p))   # (half the distance to the nearer end; then down until the rounded ends are inside)
+    while h > 0.0 and bandwidth_problem(p, h):
+        h = math.nextafter(h, 0.0)
+    if not h > 0.0:
+        raise ValueError('quantile_bandwidth: no bandwidth fits p = %r' % p)
+    return h
 
 
 def quantile_keys(x):
@@ -126,6 +172,43 @@ def quantile_keys(x):
 def quantile_rank(p, n):
     """1-based rank of quantile p among n >= 1 values: ceil of the one fp64 product p * n, clamped to [1, n]"""
     return min(max(int(math.ceil(float(p) * float(n))), 1), int(n))
+
+
+def _key_value(key):
+    """the double whose quantile key is `key` (the inverse of quantile_keys on one key)"""
+    key = np.uint64(key)
+    u = key & np.uint64((1 << 63) - 1) if key >> np.uint64(63) else ~key
+    return np.array([u], dtype=np.uint64).view(np.float64)[0]
+
+
+def _sparsity(skeys, p, h):
+    """(a, b, s) of the contract of egdst_simulate_batch_spec_cov from the sorted keys of the n qualifying values: the order
+    statistics of ranks k_lo = quantile_rank(p - h, n) and k_hi = quantile_rank(p + h, n), and the sparsity
+    s = (b - a) / ((double)(k_hi - k_lo) / (double)n), one difference and two quotients; n = 0: all NaN"""
+    n = len(skeys)
+    if n == 0:
+        return np.nan, np.nan, np.nan
+    p, h = np.float64(p), np.float64(h)
+    k_lo, k_hi = quantile_rank(p - h, n), quantile_rank(p + h, n)
+    a, b = _key_value(skeys[k_lo - 1]), _key_value(skeys[k_hi - 1])
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        s = (b - a) / (np.float64(k_hi - k_lo) / np.float64(n))
+    return a, b, s
+
+
+def quantile_band(x, p, h):
+    """(a, b, s): the order statistics Q(p - h) and Q(p + h) of the non-NaN values of x and the sparsity
+    s = (b - a) / ((k_hi - k_lo) / n), the spacing estimate of 1 / f at quantile p (Siddiqui; Bloch and Gastwirth), as
+    k_quantile_band forms it: mask, sort the keys, index.  The mirror of ModelLibrary.quantile_band_eval, bit for bit; all NaN
+    when no value qualifies, s NaN when the two ranks coincide.  ValueError on a p or a bandwidth the library refuses."""
+    p, h = float(p), float(h)
+    if not 0.0 < p < 1.0:
+        raise ValueError('quantile_band: p = %r is outside (0, 1)' % p)
+    why = 'is missing' if h == 0.0 else bandwidth_problem(p, h)
+    if why:
+        raise ValueError('quantile_band: the bandwidth %r of quantile %r %s' % (h, p, why))
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    return _sparsity(np.sort(quantile_keys(x[~np.isnan(x)])), p, h)
 
 
 def convert_records(rec, dtype):
@@ -275,6 +358,9 @@ class MomentSpec(list):
                 raise ValueError('MomentSpec: share %s has lo > hi' % what)
             if q.kind == QUANTILE and not 0.0 < q.lo < 1.0:   # (NaN fails both)
                 raise ValueError('MomentSpec: quantile %s has p = %r outside (0, 1)' % (what, q.lo))
+            if q.kind == QUANTILE and bandwidth_problem(q.lo, q.hi):
+                raise ValueError('MomentSpec: the bandwidth %r of quantile %s (p = %r) %s'
+                                 % (q.hi, what, q.lo, bandwidth_problem(q.lo, q.hi)))
             out[j] = (q.kind, col, col2, f, l_, cc, q.lo, q.hi, clo, chi, lag2, clag)
         return out
 
@@ -333,7 +419,9 @@ class MomentSpec(list):
         d_ij * d_ik: partial t < parts adds the rounded products of the agents i = t (mod parts) in ascending i, then the fixed
         tree over the partials.  parts = the library's cov_parts (4) gives the device's bits.  The row and column of an empty
         moment are NaN.  No degrees-of-freedom correction: nsim * cov estimates the asymptotic variance of the moment vector,
-        and cov of a data panel is what a user inverts into W.  Raises ValueError on a quantile, which has no covariance here."""
+        and cov of a data panel is what a user inverts into W.  A quantile enters with the influence function of the sample
+        quantile, (p - F(q)) / f(q), 1 / f estimated by the spacing of two order statistics (`scores`, quantile_band): it needs a
+        bandwidth, and its row and column are NaN where the sparsity is.  Raises ValueError on a quantile without a bandwidth."""
         if parts < 1 or parts > 256 or parts & (parts - 1):
             raise ValueError('MomentSpec.covariance: parts must be a power of two in [1, 256]')
         means, counts, d = self.scores(sims, block=block, layout=layout)
@@ -356,19 +444,32 @@ class MomentSpec(list):
         """(means [nmom], counts [nmom], d [nsim, nmom]): the moments of evaluate(sims, block) and every agent's score
         d_ij = (s_ij - m_j * c_ij) / N_j as covariance documents it -- the agent's contribution to moment j, whose cross
         products over the agents are Omega.  Elementwise IEEE operations: no summation order beyond an agent's own periods.
-        Raises ValueError on a quantile."""
+        A quantile with a bandwidth h has d_ij = (s_j * (p * c_ij - t_ij)) / N_j: t_ij the agent's qualifying pairs whose key is
+        <= the key of the quantile q_j, s_j the sparsity of quantile_band on the record's qualifying values (a product, a
+        difference, a product, a quotient); its column is NaN when s_j is (an empty record, or two ranks that coincide) and 0.0
+        when the band lies inside a mass point.  Raises ValueError on a quantile without a bandwidth."""
         sims = np.asarray(sims, dtype=np.float64)
         if sims.ndim != 3:
             raise ValueError('MomentSpec.scores: sims must be [nsim, nt, nout]')
         rec = self.pack_lag(sims.shape[1], layout)
         for j, q in enumerate(rec):
-            if q['kind'] == QUANTILE:
-                raise ValueError('MomentSpec: moment %d is a quantile, which has no covariance here' % j)
+            if q['kind'] == QUANTILE and q['hi'] == 0.0:
+                raise ValueError('MomentSpec: moment %d is a quantile without a bandwidth, which has no covariance' % j)
         means, counts = self.evaluate(sims, block=block, layout=layout)
         nsim = sims.shape[0]
         d = np.empty((nsim, len(rec)))
         for j, q in enumerate(rec):
             ok, x = _moment_term(sims, q)
+            if q['kind'] == QUANTILE:
+                keys = quantile_keys(np.where(ok, x, 0.0))   # (the pairs that do not qualify are masked below)
+                s = _sparsity(np.sort(keys[ok]), q['lo'], q['hi'])[2]
+                c = ok.sum(axis=1).astype(np.float64)
+                t = np.zeros(nsim)
+                if counts[j]:
+                    t = (ok & (keys <= quantile_keys(means[j:j + 1])[0])).sum(axis=1).astype(np.float64)
+                with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+                    d[:, j] = (np.float64(s) * (q['lo'] * c - t)) / np.float64(counts[j])
+                continue
             # s_ij: from 0.0, the qualifying values in period order (adding +0.0 for the others leaves the sum unchanged)
             s = np.cumsum(np.concatenate([np.zeros((nsim, 1)), np.where(ok, x, 0.0)], axis=1), axis=1)[:, -1]
             with np.errstate(invalid='ignore', divide='ignore'):

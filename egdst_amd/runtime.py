@@ -37,7 +37,7 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_tp_inplace', 'egdst_get_tp_tail_counts', 'egdst_get_group_profile',
                'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys', 'egdst_simulate_batch_spec_lag',
                'egdst_simulate_batch_spec_cov', 'egdst_cov_parts', 'egdst_stamp_names', 'egdst_get_stamps',
-               'egdst_policy_batch', 'egdst_policy_parts']
+               'egdst_policy_batch', 'egdst_policy_parts', 'egdst_quantile_band_eval']
 
 
 class EgdstRuntimeError(RuntimeError):
@@ -124,6 +124,8 @@ class ModelLibrary:
         L.egdst_math_eval.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.egdst_quantile_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_int)]
+        L.egdst_quantile_band_eval.argtypes = [C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.egdst_quantile_lds_keys.argtypes = []
         L.egdst_device_tables.argtypes = [C.c_void_p, C.c_int] + [C.POINTER(C.c_void_p)] * 4
         info = EgdstModelInfo()
@@ -181,6 +183,18 @@ class ModelLibrary:
         out = np.zeros(p.size)
         cnt = C.c_int(0)
         self.check(self.lib.egdst_quantile_eval(x.size, _dp(x), p.size, _dp(p), _dp(out), C.byref(cnt)))
+        return out, cnt.value
+
+    def quantile_band_eval(self, x, p, h):
+        """(out [np, 3], the number of non-NaN values): per quantile p[i] with bandwidth h[i] of the host array x the order
+        statistics a = Q(p - h), b = Q(p + h) and the sparsity s by the device's k_quantile_band (egdst_quantile_band_eval);
+        moments.quantile_band is the same on the host."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        p = np.ascontiguousarray(np.atleast_1d(p), dtype=np.float64).reshape(-1)
+        h = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(np.asarray(h, dtype=np.float64)), p.shape))
+        out = np.zeros((p.size, 3))
+        cnt = C.c_int(0)
+        self.check(self.lib.egdst_quantile_band_eval(x.size, _dp(x), p.size, _dp(p), _dp(h), _dp(out), C.byref(cnt)))
         return out, cnt.value
 
 
@@ -637,7 +651,10 @@ class Solver:
                            cov_dev=None):
         """egdst_simulate_batch_spec_cov: the moments of simulate_batch_spec and, per draw, their covariance matrix Omega
         (agent-clustered, include/egdst.h) -- spec is a moments.MomentSpec or an array of moments.MOMENT_DTYPE or
-        moments.MOMENT_LAG_DTYPE, promoted to lag records; a quantile is refused.  The *_dev arguments are device pointers
+        moments.MOMENT_LAG_DTYPE, promoted to lag records.  A quantile is taken with a bandwidth (moments.quantile(...,
+        bandwidth=h), the record's hi: the spacing estimate of the density at the quantile, 0 < p - h and p + h < 1) and refused
+        without one; its row and column of Omega are NaN in a draw where the two ranks of the band coincide or the record is
+        empty, and 0.0 where the band lies inside a mass point.  The *_dev arguments are device pointers
         (ints); with none given, returns (means [ndraw, nmom], counts [ndraw, nmom], cov [ndraw, nmom, nmom]) through torch
         tensors allocated here.  moments.MomentSpec.covariance(panel, parts=self.lib.cov_parts) is the same on the host."""
         from . import moments

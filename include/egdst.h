@@ -203,7 +203,8 @@ int egdst_simulate_batch_moments(egdst_handle *h, const double *init, int nsim, 
  *   kind 0  mean of sims[col]
  *   kind 1  mean of sims[col] * sims[col2]                      (both present)
  *   kind 2  share with lo <= sims[col] <= hi among those pairs  (a choice share: col = 4, lo = hi = k)
- *   kind 3  quantile p of sims[col], p carried in lo with 0 < p < 1 (hi and col2 are ignored): an order statistic, by exact
+ *   kind 3  quantile p of sims[col], p carried in lo with 0 < p < 1 (col2 is ignored; hi is the bandwidth of the record's
+ *           covariance, which egdst_simulate_batch_spec_cov alone reads: every other entry ignores it): an order statistic, by exact
  *           selection on the device.  The qualifying values are those of kind 0 and count is n, their number (n = 0: NaN
  *           mean, count 0).  Rank: t = p * (double)n, one fp64 product; k = (long long)ceil(t), clamped to [1, n].  The k-th
  *           smallest qualifying value (1-based) is the "mean", its bit pattern untouched: no interpolation, so the median of
@@ -274,7 +275,8 @@ int egdst_simulate_batch_spec_lag(egdst_handle *h, const double *init, int nsim,
  * cluster.  No degrees-of-freedom correction; nsim * Omega estimates the asymptotic variance.  For one period without a
  * condition Omega_jj is the population variance of the values divided by N_j; for a moment pooled over periods it is not
  * divided by the number of periods again.  It gives the efficient weighting matrix (its inverse, or a generalised inverse:
- * shares that sum to one make it singular), standard errors and the simulation-noise term of the sandwich formula.
+ * shares that sum to one make it singular), standard errors and the simulation-noise term of the sandwich formula, for specs
+ * that hold quantiles too (below).
  * For one draw, records j and k (kinds 0, 1 and 2) and agent i, every operation a rounded fp64 operation, no FMA:
  *   c_ij   the number of the agent's qualifying pairs (those egdst_moment_lag's checks accept in the record's period range);
  *   s_ij   starts at 0.0 and adds the agent's qualifying values in ascending period (kind 2 adds 1.0 or 0.0);
@@ -284,11 +286,27 @@ int egdst_simulate_batch_spec_lag(egdst_handle *h, const double *init, int nsim,
  *            partial t (0 <= t < P) starts at 0.0 and, for the agents i = t (mod P) in ascending i, p_t = p_t + (d_ij * d_ik),
  *            the product rounded, then the sum; then for o = P/2 .. 1: p[t] += p[t+o] (t < o); Omega_jk = p[0].
  *   Omega_kj carries the bits of Omega_jk.
+ * A kind-3 record j (a quantile) enters with p = lo and a bandwidth h = hi, 0 < p - h and p + h < 1 (the rounded fp64 difference
+ * and sum).  Its score is the agent-clustered influence function of the sample quantile, (p - F^(q)) / f(q), with 1 / f estimated
+ * by the spacing of two order statistics (Siddiqui; Bloch and Gastwirth); it is centred on p and not on F^, so a record's scores
+ * sum to s_j (p N_j - T_j) / N_j, T_j the sum of the t_ij: not zero, but O(1 / N).  Every operation one rounded fp64 operation:
+ *   N_j, q_j  the count and the value egdst_simulate_batch_spec_lag writes for the record (means_dev and counts_dev get these bits);
+ *   a_j, b_j  the order statistics of the same qualifying values of ranks k_lo = rank(p - h, N_j) and k_hi = rank(p + h, N_j),
+ *             rank and key order those of kind 3 above (ceil of the one product, clamped to [1, N_j]);
+ *   s_j    = (b_j - a_j) / ((double)(k_hi - k_lo) / (double)N_j)   the sparsity: one difference, one quotient of the two
+ *             conversions, one quotient.  k_hi == k_lo gives 0 / 0 = NaN, N_j = 0 gives NaN, a tie a_j == b_j with distinct ranks
+ *             0.0 (a quantile inside a mass point has variance 0, the right limit); infinite ends flow through IEEE arithmetic;
+ *   c_ij   as above;  t_ij  the number of those pairs whose key is <= the key of q_j (the integer comparison of the selection's
+ *             keys: -0.0 comes before +0.0);
+ *   d_ij   = (s_j * (p * (double)c_ij - (double)t_ij)) / (double)N_j    a product, a difference, a product and a quotient.
+ * Omega is then formed as above.
  * An empty moment (N_j = 0) has m_j = NaN and d_ij = NaN: row and column j of Omega are NaN (the payload is not part of the
- * contract).  A draw that failed to solve has counts 0, NaN means and an all-NaN Omega.
+ * contract), and so are those of a quantile whose s_j is NaN.  A draw that failed to solve has counts 0, NaN means and an
+ * all-NaN Omega.
  * EGDST_E_ARG before anything is launched, with the moment's index in egdst_last_error where a record is at fault: everything
- * egdst_simulate_batch_spec_lag refuses; a kind-3 record (a quantile has no covariance here: its influence function needs a
- * density estimate); cov_dev == NULL. */
+ * egdst_simulate_batch_spec_lag refuses; a kind-3 record with hi == 0.0 (a quantile has no covariance without a bandwidth: its
+ * influence function needs a density estimate), with hi NaN or hi <= 0, or with lo - hi <= 0 or lo + hi >= 1 (the message names
+ * the quantile and its bandwidth); cov_dev == NULL. */
 int egdst_simulate_batch_spec_cov(egdst_handle *h, const double *init, int nsim, const double *randstream_dev,
                                   long long nrand, unsigned long long seed, int rndtype,
                                   const egdst_moment_lag *spec, int nmom,
@@ -412,6 +430,12 @@ int egdst_math_eval(int fn, int n, const double *x, const double *y, double *out
  * (the other columns NaN) and k_quantiles runs on np kind-3 records.  NaNs in x do not qualify.  out [np], count [1].
  * EGDST_E_ARG if n < 1, np < 1 or a p is not inside (0, 1). */
 int egdst_quantile_eval(int n, const double *x, int np, const double *p, double *out, int *count);
+/* The band of egdst_simulate_batch_spec_cov's quantile records on the host array x, laid out as egdst_quantile_eval lays it out:
+ * k_quantile_band runs on np kind-3 records with p[i] and bandwidth h[i].  out [np][3]: the order statistics a = Q(p - h) and
+ * b = Q(p + h) and the sparsity s (all NaN when nothing qualifies); count [1].  EGDST_E_ARG for what egdst_quantile_eval refuses,
+ * for an h that is 0, NaN or negative, and for p - h <= 0 or p + h >= 1. */
+int egdst_quantile_band_eval(int n, const double *x, int np, const double *p, const double *h,
+                             double *out /* [np][3]: a, b, s */, int *count);
 /* Candidates (agents times periods of a kind-3 moment) up to which this library's k_quantiles gathers the keys into LDS
  * once; a moment with more reads its column from memory in every pass of the selection (build constant QNT_LDS_KEYS). */
 int egdst_quantile_lds_keys(void);
