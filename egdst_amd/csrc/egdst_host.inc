@@ -2,7 +2,15 @@
 // Included at the end of egdst_kernels.hip so that the whole per-model library is one translation unit.
 
 #define EGDST_MAX_GROUPS 32
+#ifndef EG_STRAGGLER_CALLS   // (-DEG_STRAGGLER_CALLS=n: a checking build may lower it)
 #define EG_STRAGGLER_CALLS 1000u
+#endif
+// -DEG_STRAGGLER_EVERY=n (checking builds): egdst_sync also takes every n-th draw (i % n == 1) for a straggler, so that a small
+// case runs straggler lanes and a permuted draw order.  The counter alone cannot single draws out there: since the fixed points
+// are fast-forwarded, Batch.work is 0 for every draw of the C2 cases, and with its floor lowered it is the same number for all.
+#ifndef EG_STRAGGLER_EVERY
+#define EG_STRAGGLER_EVERY 0
+#endif
 #define EG_ENV_WIDE_MAX_CELLS 128  // up to this many (draw, state) cells per solve k_envelope runs 512 threads wide
 #define EG_GRID_WIDE_MAX_POINTS 131072  // grid points per period up to which k_grid_wide (16 lanes per point) is used
 #if MS_ND == 1
@@ -92,6 +100,15 @@ struct egdst_handle {
     PolItem *pol_items;
     double *pol_term;
     size_t pol_obs_bytes, pol_perm_bytes, pol_flag_bytes, pol_items_bytes, pol_term_bytes;
+    // egdst_attach_panel: a panel resident on the device (the same grouping), its items indexed by period, and the terms of ALL
+    // draws, [ndraw][nobs], which every solve rewrites period by period (k_policy_period) and egdst_fit_dev reduces
+    egdst_obs *pan_obs;
+    int *pan_perm, *pan_flag;
+    PolItem *pan_items;
+    double *pan_term;
+    int *pan_first;     // host, [nt + 1]: the items of period it are pan_items[pan_first[it] .. pan_first[it + 1])
+    int pan_nobs, pan_resid;   // pan_nobs > 0: a panel is attached
+    int pan_fit;        // a solve enqueued since the attach wrote the terms, and nothing was imported since
     size_t klog_bytes;  // kink log (egdst_set_dbgout), allocated apart from the pool
     void **emu_items;  // sanitizer harness only: one heap block per array instead of the pool
     int emu_nitems;
@@ -784,10 +801,12 @@ extern "C" int egdst_destroy(egdst_handle *h)
     {
         void *simbufs[] = {h->sim_init, h->sim_rs, h->sim_sims, h->sim_means, h->sim_err, h->sim_counts,
                            h->sim_spec, h->sim_tgt, h->sim_W, h->sim_scores, h->sim_band,
-                           h->pol_obs, h->pol_perm, h->pol_flag, h->pol_items, h->pol_term};
+                           h->pol_obs, h->pol_perm, h->pol_flag, h->pol_items, h->pol_term,
+                           h->pan_obs, h->pan_perm, h->pan_flag, h->pan_items, h->pan_term};
         for (void *p : simbufs)
             if (p) (void)hipFree(p);
     }
+    free(h->pan_first);
     if (h->emu_items) {
         for (int i = 0; i < h->emu_nitems; i++) free(h->emu_items[i]);
         free(h->emu_items);
@@ -992,6 +1011,29 @@ static void enqueue_envelope(const GroupStep &s, int terminal, bool env_tp, bool
 #endif
 }
 
+// The attached panel's observations of one period for one group's draws (egdst_attach_panel): behind the period's envelope step
+// on the group's own chain, while the period's table is live.  Nothing without a panel, nothing for a period without
+// observations; not bracketed by the profile's events (its classes are the solve's).
+// (On the chain deliberately: both side-stream experiments recorded below and in enqueue_envelope lost to the cost of cross-stream events.)
+static void enqueue_panel(const GroupStep &s)
+{
+    egdst_handle *h = s.h;
+    if (!h->pan_nobs) return;
+    const int i0 = h->pan_first[s.it], nitems = h->pan_first[s.it + 1] - i0;
+    if (nitems <= 0) return;
+    PanelArgs a;
+    a.it = s.it, a.slot = (h->b.g.nslots == 2) ? (s.it & 1) : s.it;
+    a.nobs = h->pan_nobs, a.resid = h->pan_resid;
+    a.obs = h->pan_obs, a.perm = h->pan_perm, a.items = h->pan_items + i0;
+    a.term = h->pan_term, a.flag = h->pan_flag;
+    for (int l0 = 0; l0 < s.gdraws; l0 += 65535) {   // (the grid's second dimension)
+        const int nd = s.gdraws - l0 < 65535 ? s.gdraws - l0 : 65535;
+        a.lane0 = l0;
+        hipLaunchKernelGGL(k_policy_period, dim3((unsigned)nitems, (unsigned)nd), dim3(POL_BS), 0, s.gs, s.bg, a);
+    }
+    eg_after(s, "k_policy_period");
+}
+
 // Enqueues a solve on the handle's stream: the memsets, the fork to the group streams, every period's kernels per group (the
 // plan of the handle), the join.  (Measured and removed: capturing this sequence once into a hipGraph and replaying
 // it -- 19.4 ms against 19.6 ms for a single C2 solve and nothing for batches; the launches are already asynchronous.)
@@ -1066,6 +1108,7 @@ static int enqueue_solve(egdst_handle *h)
                 eg_after(st, "k_terminal");
                 enqueue_envelope(st, 1, env_tp, env_parts);
                 eg_after(st, "k_envelope(T)");
+                enqueue_panel(st);
                 continue;
             }
             if (p.sortcheck)
@@ -1087,6 +1130,7 @@ static int enqueue_solve(egdst_handle *h)
             eg_after(st, "k_grid+k_fixup");
             enqueue_envelope(st, 0, env_tp, env_parts);
             eg_after(st, "k_envelope");
+            enqueue_panel(st);
         }
     }
     if (G > 1)  // join: the handle's stream, group 0's launches on it, continues when every other group is done
@@ -1096,6 +1140,7 @@ static int enqueue_solve(egdst_handle *h)
         }
     HIPCHK(hipGetLastError());
     h->solved = 1;
+    h->pan_fit = h->pan_nobs > 0;
     if (h->imported) memset(h->imported, 0, (size_t)g.ndraw);
     return 0;
 }
@@ -1141,7 +1186,7 @@ extern "C" int egdst_sync(egdst_handle *h)
         if (hipMemcpy(h->work_h, h->b.work, sizeof(unsigned) * h->b.g.ndraw, hipMemcpyDeviceToHost) == hipSuccess) {
             int changed = 0, ns = 0;
             for (int i = 0; i < h->b.g.ndraw; i++) {
-                const unsigned char sl = h->work_h[i] > EG_STRAGGLER_CALLS ? 1 : 0;
+                const unsigned char sl = (h->work_h[i] > EG_STRAGGLER_CALLS || (EG_STRAGGLER_EVERY && i % (EG_STRAGGLER_EVERY ? EG_STRAGGLER_EVERY : 1) == 1)) ? 1 : 0;
                 if (sl != h->strag_h[i]) changed = 1;
                 h->strag_h[i] = sl;
                 ns += sl;
@@ -1358,6 +1403,7 @@ static int import_begin(egdst_handle *h, int draw)
         h->imported = (unsigned char *)calloc((size_t)g.ndraw, 1);
         if (!h->imported) return set_err(EGDST_E_ARG, "solution import: out of host memory");
     }
+    h->pan_fit = 0;   // (egdst_fit_dev answers for solves alone: the terms on the handle are not those of an imported table)
     if (h->imported[draw]) return 0;
     int st = EGDST_E_NOT_SOLVED;
     if (!h->solved) {
@@ -1746,6 +1792,47 @@ static_assert(sizeof(egdst_obs) == 40 && offsetof(egdst_obs, cash) == 16 && offs
 
 extern "C" int egdst_policy_parts(void) { return POL_BS; }
 
+#if MS_NCONT == 0
+// The per-observation checks of egdst_policy_batch and egdst_attach_panel, with the observation's index in the message.
+static int pol_check_obs(const char *who, const Geom &g, const egdst_obs *obs, int nobs, int resid)
+{
+    for (int k = 0; k < nobs; k++) {
+        const egdst_obs &o = obs[k];
+        const char *bad = nullptr;
+        if (o.it < 0 || o.it >= g.nt) bad = "it is outside the model's periods";
+        else if (o.ist < 0 || o.ist >= MS_NST) bad = "ist is outside the model's states";
+        else if (o.id < -1 || o.id >= MS_ND) bad = "id is outside the model's decisions (-1: not observed)";
+        else if (o.reserved != 0) bad = "reserved is not 0";
+        else if (!(o.cash >= g.a0)) bad = "cash is NaN or below a0";   // (above mmax the policy is extrapolated, as the simulator does from its second period on)
+        else if (!(o.w >= 0.0)) bad = "w is NaN or negative";
+        else if (resid == 1 && o.cons <= 0.0) bad = "resid = 1 with a consumption that is not positive";
+        if (bad) return set_err(EGDST_E_ARG, "%s: observation %d: %s", who, k, bad);
+    }
+    return 0;
+}
+
+// The grouping of both doors: a counting sort by cell keeps the caller's order inside a cell (perm), and every cell's run of the
+// permutation is cut into items of at most POL_BS observations, in cell order -- so a period's items are one contiguous range.
+static void pol_group(const Geom &g, const egdst_obs *obs, int nobs, std::vector<int> &perm, std::vector<PolItem> &items)
+{
+    const int ncell = g.nt * MS_NST;
+    std::vector<int> first((size_t)ncell + 1, 0);
+    perm.assign((size_t)nobs, 0);
+    for (int k = 0; k < nobs; k++) first[(size_t)obs[k].it * MS_NST + obs[k].ist + 1]++;
+    for (int c = 0; c < ncell; c++) first[c + 1] += first[c];
+    {
+        std::vector<int> next(first.begin(), first.end() - 1);
+        for (int k = 0; k < nobs; k++) perm[next[(size_t)obs[k].it * MS_NST + obs[k].ist]++] = k;
+    }
+    items.clear();
+    for (int c = 0; c < ncell; c++)
+        for (int f = first[c]; f < first[c + 1]; f += POL_BS) {
+            const int left = first[c + 1] - f;
+            items.push_back(PolItem{c / MS_NST, c % MS_NST, f, left < POL_BS ? left : POL_BS});
+        }
+}
+#endif
+
 extern "C" int egdst_policy_batch(egdst_handle *h, const egdst_obs *obs, int nobs, int resid, double *cons_dev, int *id_dev,
                                   double *vf_dev, double *ssr_dev, int *hits_dev)
 {
@@ -1760,40 +1847,18 @@ extern "C" int egdst_policy_batch(egdst_handle *h, const egdst_obs *obs, int nob
     if (!h->solved) return set_err(EGDST_E_NOT_SOLVED, "%s", egdst_strerror(EGDST_E_NOT_SOLVED));
     if (!h->params_set && MS_NPARAM) return set_err(EGDST_E_ARG, "%s: parameters not set", who);
     const Geom &g = h->b.g;
-    for (int k = 0; k < nobs; k++) {
-        const egdst_obs &o = obs[k];
-        const char *bad = nullptr;
-        if (o.it < 0 || o.it >= g.nt) bad = "it is outside the model's periods";
-        else if (o.ist < 0 || o.ist >= MS_NST) bad = "ist is outside the model's states";
-        else if (o.id < -1 || o.id >= MS_ND) bad = "id is outside the model's decisions (-1: not observed)";
-        else if (o.reserved != 0) bad = "reserved is not 0";
-        else if (!(o.cash >= g.a0)) bad = "cash is NaN or below a0";   // (above mmax the policy is extrapolated, as the simulator does from its second period on)
-        else if (!(o.w >= 0.0)) bad = "w is NaN or negative";
-        else if (resid == 1 && o.cons <= 0.0) bad = "resid = 1 with a consumption that is not positive";
-        if (bad) return set_err(EGDST_E_ARG, "%s: observation %d: %s", who, k, bad);
-    }
-    // the grouping: a counting sort by cell keeps the caller's order inside a cell
-    const int ncell = g.nt * MS_NST;
-    std::vector<int> first((size_t)ncell + 1, 0), perm((size_t)nobs);
-    for (int k = 0; k < nobs; k++) first[(size_t)obs[k].it * MS_NST + obs[k].ist + 1]++;
-    for (int c = 0; c < ncell; c++) first[c + 1] += first[c];
-    {
-        std::vector<int> next(first.begin(), first.end() - 1);
-        for (int k = 0; k < nobs; k++) perm[next[(size_t)obs[k].it * MS_NST + obs[k].ist]++] = k;
-    }
+    int rc = pol_check_obs(who, g, obs, nobs, resid);
+    if (rc) return rc;
+    std::vector<int> perm;
     std::vector<PolItem> items;
-    for (int c = 0; c < ncell; c++)
-        for (int f = first[c]; f < first[c + 1]; f += POL_BS) {
-            const int left = first[c + 1] - f;
-            items.push_back(PolItem{c / MS_NST, c % MS_NST, f, left < POL_BS ? left : POL_BS});
-        }
+    pol_group(g, obs, nobs, perm, items);
     const bool fit = ssr_dev || hits_dev;
     const size_t per_draw = (sizeof(double) + sizeof(int)) * (size_t)nobs;
     int slice = fit ? (int)(EG_POL_SLICE_BYTES / per_draw) : g.ndraw;
     if (slice > 65535) slice = 65535;
     if (slice < 1) slice = 1;
     if (slice > g.ndraw) slice = g.ndraw;
-    int rc = sim_reserve((void **)&h->pol_obs, &h->pol_obs_bytes, sizeof(egdst_obs) * (size_t)nobs);
+    rc = sim_reserve((void **)&h->pol_obs, &h->pol_obs_bytes, sizeof(egdst_obs) * (size_t)nobs);
     if (!rc) rc = sim_reserve((void **)&h->pol_perm, &h->pol_perm_bytes, sizeof(int) * (size_t)nobs);
     if (!rc) rc = sim_reserve((void **)&h->pol_items, &h->pol_items_bytes, sizeof(PolItem) * items.size());
     if (!rc && fit) rc = sim_reserve((void **)&h->pol_term, &h->pol_term_bytes, sizeof(double) * (size_t)nobs * slice);
@@ -1828,6 +1893,104 @@ extern "C" int egdst_policy_batch(egdst_handle *h, const egdst_obs *obs, int nob
     if (e != hipSuccess || e2 != hipSuccess) return set_err(EGDST_E_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : e2));
     return 0;
 #endif
+}
+
+// The resident panel (include/egdst.h): egdst_policy_batch's checks and grouping, done once; the observations, the permutation and
+// the items stay on the device, the host keeps where each period's items begin, and the terms of every (draw, observation) have
+// storage of their own, which the solves fill (enqueue_panel) and egdst_fit_dev reduces with k_policy_fit.  A one-time host call:
+// it waits for the handle's stream, since a solve still running there reads the panel it replaces.
+static void panel_free(egdst_handle *h)
+{
+    void *bufs[] = {h->pan_obs, h->pan_perm, h->pan_flag, h->pan_items, h->pan_term};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
+    h->pan_obs = nullptr, h->pan_perm = nullptr, h->pan_flag = nullptr, h->pan_items = nullptr, h->pan_term = nullptr;
+    free(h->pan_first);
+    h->pan_first = nullptr;
+    h->pan_nobs = h->pan_resid = h->pan_fit = 0;
+}
+
+extern "C" int egdst_attach_panel(egdst_handle *h, const egdst_obs *obs, int nobs, int resid)
+{
+    const char *who = "egdst_attach_panel";
+    if (!h || nobs < 0 || (!obs) != (nobs == 0)) return set_err(EGDST_E_ARG, "%s: bad arguments", who);
+    if (!obs) {   // detach
+        HIPCHK(hipStreamSynchronize(h->stream));
+        panel_free(h);
+        return 0;
+    }
+#if MS_NCONT > 0
+    return set_err(EGDST_E_ARG, "%s: a model with continuous states is not served (its policy is a blend over grid corners)", who);
+#else
+    if (resid != 0 && resid != 1) return set_err(EGDST_E_ARG, "%s: resid is not 0 or 1", who);
+    const Geom &g = h->b.g;
+    int rc = pol_check_obs(who, g, obs, nobs, resid);
+    if (rc) return rc;
+    std::vector<int> perm;
+    std::vector<PolItem> items;
+    pol_group(g, obs, nobs, perm, items);
+    int *first = (int *)malloc(sizeof(int) * ((size_t)g.nt + 1));
+    if (!first) return set_err(EGDST_E_HIP, "%s: out of host memory", who);
+    {   // items are in cell order, so in period order
+        size_t i = 0;
+        for (int it = 0; it <= g.nt; it++) {
+            while (i < items.size() && items[i].it < it) i++;
+            first[it] = (int)i;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    panel_free(h);
+    const size_t pairs = (size_t)nobs * g.ndraw;
+    struct { void **p; size_t bytes; const void *src; } bufs[] = {
+        {(void **)&h->pan_obs, sizeof(egdst_obs) * (size_t)nobs, obs},
+        {(void **)&h->pan_perm, sizeof(int) * (size_t)nobs, perm.data()},
+        {(void **)&h->pan_items, sizeof(PolItem) * items.size(), items.data()},
+        {(void **)&h->pan_term, sizeof(double) * pairs, nullptr},
+        {(void **)&h->pan_flag, sizeof(int) * pairs, nullptr}};
+    for (auto &bf : bufs) {
+        hipError_t e = hipMalloc(bf.p, bf.bytes);
+        if (e == hipSuccess && bf.src) e = hipMemcpy(*bf.p, bf.src, bf.bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();   // (the failure is reported here: it is not left for the next launch's check to find)
+            panel_free(h);
+            free(first);
+            return set_err(EGDST_E_HIP, "%s: %zu bytes on the device (%d observations x %d draws): %s", who, bf.bytes, nobs, g.ndraw,
+                           hipGetErrorString(e));
+        }
+    }
+    h->pan_first = first;
+    h->pan_nobs = nobs, h->pan_resid = resid;
+    h->pan_fit = 0;   // (no fit until the next solve has written the terms)
+    return 0;
+#endif
+}
+
+extern "C" int egdst_fit_dev(egdst_handle *h, double *ssr_dev, int *hits_dev)
+{
+    if (!h || (!ssr_dev && !hits_dev)) return set_err(EGDST_E_ARG, "egdst_fit_dev: bad arguments");
+    if (!h->pan_nobs) return set_err(EGDST_E_ARG, "egdst_fit_dev: no panel is attached (egdst_attach_panel)");
+    if (!h->pan_fit) return set_err(EGDST_E_NOT_SOLVED, "egdst_fit_dev: no solve since the panel was attached or a solution was imported");
+    const Batch *bdev = nullptr;
+    int rc = batch_for_call(h, &bdev);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_policy_fit, dim3(h->b.g.ndraw), dim3(POL_BS), 0, h->stream, bdev, 0, h->pan_nobs, (const double *)h->pan_term,
+                       (const int *)h->pan_flag, ssr_dev, hits_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int egdst_get_fit(egdst_handle *h, double *ssr, int *hits)
+{
+    if (!h || (!ssr && !hits)) return set_err(EGDST_E_ARG, "egdst_get_fit: bad arguments");
+    // (staged in the handle's objective buffer, 2 x ndraw doubles: ssr in its first half, hits in its second)
+    double *ssr_dev = h->b.obj;
+    int *hits_dev = (int *)(h->b.obj + h->b.g.ndraw);
+    int rc = egdst_fit_dev(h, ssr_dev, hits_dev);
+    if (rc) return rc;
+    if (ssr) HIPCHK(hipMemcpyAsync(ssr, ssr_dev, sizeof(double) * h->b.g.ndraw, hipMemcpyDeviceToHost, h->stream));
+    if (hits) HIPCHK(hipMemcpyAsync(hits, hits_dev, sizeof(int) * h->b.g.ndraw, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
 }
 
 // egdst_call.c:17-164.  The index checks of the gateway are done here, in row order, because an out-of-range index

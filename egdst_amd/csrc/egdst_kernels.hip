@@ -4811,6 +4811,26 @@ struct PolArgs {
     int *flag;                 // beside them: -1 no policy here (the cell is missing), else bit 0 the term counts, bit 1 a hit
 };
 
+// The term of one (observation, draw) in the fit and its flag, the one place it is formed (k_policy_obs, k_policy_period): have =
+// the cell has a policy, c and id what eg_policy_at gave.  Every operation a rounded fp64 operation (include/egdst.h).
+static __device__ __forceinline__ int eg_policy_term(const egdst_obs &o, bool have, double c, int id, int resid, double *term_out)
+{
+    double term = 0.0;
+    int fl = -1;
+    if (have) {
+        fl = 0;
+        if (o.cons == o.cons && o.w != 0.0) {   // (consumption observed, and weighted)
+            const double r = resid ? MS_LOG(o.cons) - MS_LOG(c) : o.cons - c;
+            const double r2 = r * r;
+            term = o.w * r2;
+            fl = 1;
+        }
+        if (o.id >= 0 && o.id == id) fl |= 2;
+    }
+    *term_out = term;
+    return fl;
+}
+
 // One lane per (observation, draw of the launch).  A workgroup serves observations of ONE cell of one draw (the host's items), so
 // the table's address, its lengths and the model's environment are uniform over the workgroup and its lanes search one column,
 // where it lies, in global memory, by the routine k_simulate uses.  Results go to the caller's index.
@@ -4845,22 +4865,54 @@ __global__ void __launch_bounds__(POL_BS) k_policy_obs(const Batch *bp_, PolArgs
     if (a.id) a.id[at] = id;
     if (a.vf) a.vf[at] = vf;
     if (a.term) {
-        double term = 0.0;
-        int fl = -1;
-        if (have) {
-            fl = 0;
-            if (o.cons == o.cons && o.w != 0.0) {   // (consumption observed, and weighted)
-                const double r = a.resid ? MS_LOG(o.cons) - MS_LOG(c) : o.cons - c;
-                const double r2 = r * r;
-                term = o.w * r2;
-                fl = 1;
-            }
-            if (o.id >= 0 && o.id == id) fl |= 2;
-        }
         const size_t st = (size_t)blockIdx.y * a.nobs + k;
-        a.term[st] = term;
-        a.flag[st] = fl;
+        a.flag[st] = eg_policy_term(o, have, c, id, a.resid, &a.term[st]);
     }
+#endif
+}
+
+// The same at the observations of ONE period, inside a solve (egdst_attach_panel, include/egdst.h): launched on a draw group's own
+// stream behind the period's envelope step, when the table of period `it` is complete and live in `slot` (it & 1 on a handle
+// without history, whose slot period it - 2 overwrites).  A workgroup serves one cell of one draw, as in k_policy_obs; the draws are
+// those of the group's range of the schedule (lane0: a range of more than 65 535 draws takes several launches).  Terms and flags go
+// to the draw's TRUE index and the caller's observation index, [ndraw][nobs], where k_policy_fit reads them after the solve: the
+// schedule and the grouping show in no bit.  A draw whose status is already set writes "no policy" (its final status decides).
+struct PanelArgs {
+    int it, slot, lane0, nobs, resid;
+    const egdst_obs *obs;      // [nobs], the caller's order
+    const int *perm;           // [nobs] the observations grouped by cell, stable
+    const PolItem *items;      // the items of period `it` (gridDim.x of them)
+    double *term;              // [ndraw][nobs]
+    int *flag;
+};
+__global__ void __launch_bounds__(POL_BS) k_policy_period(const Batch *bp_, PanelArgs a)
+{
+#if MS_NCONT == 0   // (continuous states: the host refuses the panel)
+    BatchRef b = EG_BATCH_REF(bp_);
+    const PolItem w = a.items[blockIdx.x];
+    const int draw = b.order[b.draw0 + a.lane0 + (int)blockIdx.y];
+    if ((int)threadIdx.x >= w.count) return;
+    const int k = a.perm[w.first + threadIdx.x];
+    const egdst_obs o = a.obs[k];
+    Tab t = {};
+    if (b.status[draw] == 0) t = eg_tab(b, a.slot, draw, w.ist);
+    const bool have = t.len >= 2;
+    double c = NAN, vf = NAN;
+    int id = -1;
+    if (have) {
+        ms_env E = eg_env(b, draw);
+        ms_pv cp;
+        cp.it = a.it;
+        cp.ist = w.ist;
+        cp.id = 0;
+        cp.cash = o.cash;
+        cp.savings = 0;
+        cp.shock = NAN;
+        c = eg_policy_at(&E, &cp, t.M, t.C, t.V, t.TH, t.D, t.len, t.thlen, &vf);
+        id = cp.id;
+    }
+    const size_t st = (size_t)draw * a.nobs + k;
+    a.flag[st] = eg_policy_term(o, have, c, id, a.resid, &a.term[st]);
 #endif
 }
 

@@ -1,7 +1,12 @@
 """The fit to micro data: observations of a data panel for egdst_policy_batch (include/egdst.h), and the host mirrors the tests
 hold the device to -- the policy in numpy from an exported solution, operation for operation as the device's bracket search and
 interpolation (csrc/egdst_device.h: eg_bracket, eg_lerp; csrc/egdst_kernels.hip: eg_policy_at), and the fit in the summation
-order of the contract.  Nothing here runs on the estimation path: Solver.policy_batch does."""
+order of the contract.  Nothing here runs on the estimation path: Solver.policy_batch does.
+
+The same observations can stay on a handle (egdst_attach_panel: Solver.attach_panel, fit_dev, fit): every solve then evaluates them
+period by period while the period's table is live, so the fit needs no history and no host synchronisation -- the form for an
+estimation loop over a large batch.  Its ssr and hits are egdst_policy_batch's bit for bit, so fit_mirror below is the contract
+of both doors; the predictions themselves (cons, id, vf) remain policy_batch's."""
 from __future__ import annotations
 
 import ctypes as C

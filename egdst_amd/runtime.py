@@ -37,7 +37,8 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_tp_inplace', 'egdst_get_tp_tail_counts', 'egdst_get_group_profile',
                'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys', 'egdst_simulate_batch_spec_lag',
                'egdst_simulate_batch_spec_cov', 'egdst_cov_parts', 'egdst_stamp_names', 'egdst_get_stamps',
-               'egdst_policy_batch', 'egdst_policy_parts', 'egdst_quantile_band_eval']
+               'egdst_policy_batch', 'egdst_policy_parts', 'egdst_quantile_band_eval',
+               'egdst_attach_panel', 'egdst_fit_dev', 'egdst_get_fit']
 
 
 class EgdstRuntimeError(RuntimeError):
@@ -97,6 +98,9 @@ class ModelLibrary:
         L.egdst_cov_parts.argtypes = []
         L.egdst_policy_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.egdst_policy_parts.argtypes = []
+        L.egdst_attach_panel.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.egdst_fit_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.egdst_get_fit.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
         L.egdst_uniform.restype = C.c_double
         L.egdst_uniform.argtypes = [C.c_ulonglong, C.c_ulonglong]
         L.egdst_set_dbgout.argtypes = [C.c_void_p, C.c_int]
@@ -689,6 +693,33 @@ class Solver:
         self.lib.check(self.lib.lib.egdst_policy_batch(self.h, rec.ctypes.data_as(C.c_void_p), len(rec), int(resid),
                                                        *[C.c_void_p(ptr[k]) if ptr[k] else None for k in self.POLICY_OUTPUTS]))
         return out
+
+    def attach_panel(self, obs, resid=0):
+        """egdst_attach_panel: keep a data panel (a datafit.Observations or an array of datafit.OBS_DTYPE) on the handle; every
+        solve from now on evaluates it period by period, with or without history, and fit_dev / fit hand back what
+        policy_batch(want=('ssr', 'hits')) gives on a kept-history handle, bit for bit.  Checked as policy_batch checks;
+        attaching again replaces the panel.  No fit until the next solve."""
+        from . import datafit
+        rec = datafit.records(obs)
+        if len(rec) == 0:   # (an empty panel is refused, as policy_batch refuses it: detaching is detach_panel's)
+            raise EgdstRuntimeError(1, 'attach_panel: no observations')
+        self.lib.check(self.lib.lib.egdst_attach_panel(self.h, rec.ctypes.data_as(C.c_void_p), len(rec), int(resid)))
+
+    def detach_panel(self):
+        """free the attached panel: the solves enqueue what they did before it"""
+        self.lib.check(self.lib.lib.egdst_attach_panel(self.h, None, 0, 0))
+
+    def fit_dev(self, ssr_ptr, hits_ptr):
+        """egdst_fit_dev: ssr (float64 [ndraw]) and hits (int32 [ndraw]) of the attached panel into device buffers (ints, either
+        may be None), enqueued behind the solve on the handle's stream without a host synchronisation.  Of THIS handle's draws:
+        a draw redone after a capacity overflow reads as failed (NaN, -1), as in policy_batch."""
+        self.lib.check(self.lib.lib.egdst_fit_dev(self.h, C.c_void_p(ssr_ptr) if ssr_ptr else None, C.c_void_p(hits_ptr) if hits_ptr else None))
+
+    def fit(self):
+        """(ssr [ndraw] float64, hits [ndraw] int32) host arrays of the attached panel's fit (egdst_get_fit; synchronises)"""
+        ssr, hits = np.zeros(self.ndraw), np.zeros(self.ndraw, dtype=np.int32)
+        self.lib.check(self.lib.lib.egdst_get_fit(self.h, _dp(ssr), _ip(hits)))
+        return ssr, hits
 
     def call(self, sw, args, draw=0):
         """egdst_call gateway (egdst_call.c:17-164): sw 1 utility, 2 marginal utility, 3 discount, 4 budget, 5 marginal

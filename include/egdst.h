@@ -359,6 +359,31 @@ int egdst_policy_batch(egdst_handle *h, const egdst_obs *obs /* host, [nobs] */,
 /* The number B of partial sums of the fit's summation order (build constant POL_BS: the threads of k_policy_fit's workgroup), a
  * power of two. */
 int egdst_policy_parts(void);
+
+/* The same fit with the panel RESIDENT on the handle and evaluated inside the solve, for an estimation loop that solves thousands
+ * of times against one panel (egdst_set_params_dev, egdst_solve_async, egdst_fit_dev back to back, no host synchronisation).
+ * egdst_attach_panel checks obs (HOST memory, [nobs]) and resid as egdst_policy_batch does -- every refusal of that door that
+ * concerns the observations, resid or the model, with the same messages; nothing is kept when one fails -- and uploads once the
+ * observations, their grouping by cell and period, and reserves the terms of every (draw, observation), 12 bytes each: if the
+ * device cannot give them, EGDST_E_HIP with the bytes asked for in egdst_last_error and no panel attached.  Works with
+ * keep_history 0 and 1 and before or after a solve; a one-time host call that waits for the handle's stream.  Attaching again
+ * replaces the panel; obs == NULL with nobs == 0 detaches and frees it.  While a panel is attached, every solve evaluates the
+ * observations of period it on the period's table right behind that period's envelope step, on the draw groups' own streams --
+ * on a handle without history that is while the table is live -- one more launch per group and period with observations; without a
+ * panel a solve enqueues what it always did.
+ * egdst_fit_dev enqueues the reduction on the handle's stream behind the solve and returns without waiting (the contract of
+ * egdst_objective_dev): ssr_dev and hits_dev are DEVICE buffers [ndraw], either may be NULL, not both.  The values are those of
+ * egdst_policy_batch's ssr_dev and hits_dev on a kept-history handle with the same draws, bit for bit: its terms, its skips, its
+ * summation order over the caller's indices with egdst_policy_parts() partials, hits an exact count, NaN and -1 for a draw that
+ * failed (on a compact handle a draw stopped by EGDST_E_CAPACITY reads as failed), NaN ssr for a draw with an observation in a
+ * cell of fewer than 2 rows.  The draw groups, their order and the grouping of the observations change no bit.
+ * EGDST_E_ARG without an attached panel or with both outputs NULL; EGDST_E_NOT_SOLVED when no solve was enqueued since the
+ * attach, or a solution was imported since (egdst_set_cell_M / _D, egdst_set_solution: the fit answers for solves alone).
+ * egdst_get_fit is the host form (ssr, hits: HOST [ndraw], either may be NULL); it waits for the stream. */
+int egdst_attach_panel(egdst_handle *h, const egdst_obs *obs /* host, [nobs]; NULL with nobs 0: detach */, int nobs, int resid);
+int egdst_fit_dev(egdst_handle *h, double *ssr_dev /* [ndraw] */, int *hits_dev /* [ndraw] */);
+int egdst_get_fit(egdst_handle *h, double *ssr /* host, [ndraw] */, int *hits /* host, [ndraw] */);
+
 /* Uniform number k of stream `seed` (host replay of the device generator): with z = seed + (k+1)*0x9E3779B97F4A7C15,
  * z = (z ^ z>>30)*0xBF58476D1CE4E5B9, z = (z ^ z>>27)*0x94D049BB133111EB, z ^= z>>31 (splitmix64): (z >> 11) * 2^-53. */
 double egdst_uniform(unsigned long long seed, unsigned long long k);
