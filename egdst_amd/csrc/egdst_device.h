@@ -180,6 +180,8 @@ struct Batch {
     double *klog;         // kink log (the gateway's dbgout): [(it*ndraw+draw)*MS_NST+ist][kcap][4], or nullptr (egdst_set_dbgout)
     int *kcnt, kcap;      // kinks recorded per cell; capacity of a cell's slice
     unsigned *segstat;    // [2*ndraw] walks of the draw that were cut into segments and merged / that fell back to one wave
+    unsigned *sortstat;   // [4*ndraw] LDS sorts of the draw's envelope jobs (blk_sort_lds) by kind: lists in order / network / counting ranks;
+                          // and those of them in which two or more threads each saw a pair out of order
     int noseg;            // 1: envelope walks are never cut into segments (environment EGDST_NOSEG at create; diagnostics)
     double *obj;          // [2*ndraw] staging of k_objective for the host-returning entry point
     unsigned long long *algbytes;  // [ndraw] compulsory table traffic: 24 B per next-period row read once per

@@ -495,7 +495,7 @@ extern "C" int egdst_create_compact(const egdst_desc *d, int ndraw, int keep_his
         {(void **)&b.status, sizeof(int) * ndraw}, {(void **)&b.where, sizeof(int) * 2 * ndraw},
         {(void **)&b.evals, sizeof(unsigned long long) * ndraw},
         {(void **)&b.credited, sizeof(unsigned long long) * ndraw},
-        {(void **)&b.segstat, sizeof(unsigned) * 2 * ndraw},
+        {(void **)&b.segstat, sizeof(unsigned) * 2 * ndraw}, {(void **)&b.sortstat, sizeof(unsigned) * 4 * ndraw},
         {(void **)&b.dbg, sizeof(int) * 16 * ndraw},
         {(void **)&b.algbytes, sizeof(unsigned long long) * ndraw},
         {(void **)&b.obj, sizeof(double) * 2 * ndraw},
@@ -1048,6 +1048,7 @@ static int enqueue_solve(egdst_handle *h)
     HIPCHK(hipMemsetAsync(b.evals, 0, sizeof(unsigned long long) * g.ndraw, s));
     HIPCHK(hipMemsetAsync(b.credited, 0, sizeof(unsigned long long) * g.ndraw, s));
     HIPCHK(hipMemsetAsync(b.segstat, 0, sizeof(unsigned) * 2 * g.ndraw, s));
+    HIPCHK(hipMemsetAsync(b.sortstat, 0, sizeof(unsigned) * 4 * g.ndraw, s));
     EG_STAMP_DECL(HIPCHK(hipMemsetAsync(b.stamps, 0, sizeof(unsigned long long) * EG_NSTAMP * g.ndraw, s));)
     HIPCHK(hipMemsetAsync(b.algbytes, 0, sizeof(unsigned long long) * g.ndraw, s));
     HIPCHK(hipMemsetAsync(b.tlen, 0, sizeof(int) * (size_t)g.nslots * g.ndraw * MS_NST, s));
@@ -2449,6 +2450,14 @@ extern "C" int egdst_get_walk_stats(egdst_handle *h, unsigned *out)
     if (!h || !out) return set_err(EGDST_E_ARG, "egdst_get_walk_stats: bad arguments");
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(out, h->b.segstat, sizeof(unsigned) * 2 * h->b.g.ndraw, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int egdst_get_sort_stats(egdst_handle *h, unsigned *out)
+{
+    if (!h || !out) return set_err(EGDST_E_ARG, "egdst_get_sort_stats: bad arguments");
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(out, h->b.sortstat, sizeof(unsigned) * 4 * h->b.g.ndraw, hipMemcpyDeviceToHost));
     return 0;
 }
 

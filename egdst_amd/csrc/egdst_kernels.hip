@@ -2274,12 +2274,16 @@ static __device__ __forceinline__ void blk_rank_sort(int npts, int nf, const dou
 // also all the envelope walk's pre-classification needs to evaluate the function at the point (env_preclass): when
 // the lists are in order the class word is computed right here from the staged keys (cls != nullptr; *fused = 1),
 // `ana(g, x)` being the value of g before its first point (env_analytic / -inf).
+// *kind says which way the sort went: 0 the lists were in order (merge / ranks), 1 bitonic network, 2 counting ranks (a stream out
+// of order whose padded size does not fit lcap); | 4 when two or more threads each saw a pair out of order.  Network and counting
+// ranks sort by pt_before, a strict total order with the input index as its last tie-break, so they give the same permutation;
+// the network is the cheaper one whenever it fits.
 template <class ANA>
 static __device__ __forceinline__ eg_ldss *blk_sort_lds(int npts, int nf, const double *im, const double *ic,
                                                         const double *iv, const int *ifn, const eg_ldsi *fstart,
                                                         const eg_ldsi *dims, eg_ldsd *R1, eg_ldsd *R2, eg_ldsd *R3,
                                                         eg_ldss *Lf, eg_ldss *Lp, int lcap, int *sh, int *oob,
-                                                        eg_ldsi *cls, int *fused, ANA ana, int *dbg EG_STAMP_PARAM)
+                                                        eg_ldsi *cls, int *fused, int *kind, ANA ana, int *dbg EG_STAMP_PARAM)
 {
     eg_ldsd *Km = R1, *Kv = R2, *Lm = R2, *Lv = R3, *Lc = R1;
     const int tid = threadIdx.x;
@@ -2293,11 +2297,13 @@ static __device__ __forceinline__ eg_ldss *blk_sort_lds(int npts, int nf, const 
     int bad = 0;
     for (int i = tid + 1; i < npts; i += ENV_BS)
         if (ifn[i] == ifn[i - 1] && !pt_before(Km[i - 1], Kv[i - 1], ifn[i - 1], i - 1, Km[i], Kv[i], ifn[i], i)) bad = 1;
-    bad = blk_sum(bad, sh);
+    const int nbad = blk_sum(bad, sh);  // (threads that saw a pair out of order: a flag from here on)
+    bad = nbad ? 1 : 0;
     int P = 1;
     while (P < npts) P <<= 1;
     if (bad && P > lcap) bad = 2;  // no room for the padded network: counting ranks instead
     EG_CENSUS_BAD(bad);
+    *kind = bad | (nbad > 1 ? 4 : 0);
     EG_STAMP_BLOCK(sort, stp, EG_ST_SORT_STAGE, t3_);  // staging + order check
     if (bad != 1) {
         double kbound = INFINITY;  // min over the functions of their last grid value (:1266-1271)
@@ -3266,8 +3272,13 @@ static __device__ __forceinline__ void eg_envelope_cell(BatchRef b, int it, int 
 #endif
         int fused = 0;
         if (job.npts <= lcap) {
+            int kind = 0;
             const eg_ldss *posl = blk_sort_lds(job.npts, job.nf, iM, iC, iV, iF, fstart, fdims, R1, R2, R3, Lf, Lr, lcap,
-                                               sh, &s_oob, Lq, &fused, ana, job.dbg EG_STAMP_ARG(job.stp));
+                                               sh, &s_oob, Lq, &fused, &kind, ana, job.dbg EG_STAMP_ARG(job.stp));
+            if (tid == 0) {
+                atomicAdd(&b.sortstat[4 * (size_t)draw + (kind & 3)], 1u);
+                if (kind & 4) atomicAdd(&b.sortstat[4 * (size_t)draw + 3], 1u);
+            }
             EG_STAMP_LANE(env, tid == 0, job.stp, EG_ST_ENV_SORT, stamp_);  // LDS sort
 #ifdef EGDST_CENSUS
             cz_sort1_ = wall_clock64();

@@ -33,7 +33,7 @@ ABI_SYMBOLS = ['egdst_get_model_info', 'egdst_strerror', 'egdst_last_error', 'eg
                'egdst_get_profile', 'egdst_objective_dev', 'egdst_get_objective', 'egdst_get_params',
                'egdst_create_compact', 'egdst_geometry', 'egdst_set_groups', 'egdst_set_adaptive', 'egdst_get_schedule', 'egdst_get_work', 'egdst_get_regenerations', 'egdst_call', 'egdst_simulate_moments',
                'egdst_get_checksums', 'egdst_math_eval', 'egdst_get_evals_credited', 'egdst_simulate_batch_moments',
-               'egdst_uniform', 'egdst_set_dbgout', 'egdst_get_dbgout', 'egdst_get_walk_stats',
+               'egdst_uniform', 'egdst_set_dbgout', 'egdst_get_dbgout', 'egdst_get_walk_stats', 'egdst_get_sort_stats',
                'egdst_set_cell_M', 'egdst_set_cell_D', 'egdst_set_solution', 'egdst_get_tp_stats', 'egdst_get_tp_inplace', 'egdst_get_tp_tail_counts', 'egdst_get_group_profile',
                'egdst_simulate_batch_spec', 'egdst_quantile_eval', 'egdst_quantile_lds_keys', 'egdst_simulate_batch_spec_lag',
                'egdst_simulate_batch_spec_cov', 'egdst_cov_parts', 'egdst_stamp_names', 'egdst_get_stamps',
@@ -296,6 +296,13 @@ class Solver:
         """[ndraw, 2]: envelope walks cut into segments and merged / fallen back to one wave (egdst_get_walk_stats)"""
         out = np.zeros((self.ndraw, 2), dtype=np.uint32)
         self.lib.check(self.lib.lib.egdst_get_walk_stats(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sort_stats(self):
+        """[ndraw, 4]: LDS sorts of the last solve's envelope jobs with the lists in order / through the network / by counting ranks, and those
+        of them with two or more pairs out of order seen by different threads (egdst_get_sort_stats)"""
+        out = np.zeros((self.ndraw, 4), dtype=np.uint32)
+        self.lib.check(self.lib.lib.egdst_get_sort_stats(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def tp_stats(self):

@@ -469,6 +469,11 @@ int egdst_quantile_lds_keys(void);
  * out[2*draw+1] = walks whose segment predictions failed the check and were redone by one wave (results are the same
  * either way; environment EGDST_NOSEG=1 at create turns the cutting off). */
 int egdst_get_walk_stats(egdst_handle *h, unsigned *out /* [2*ndraw] */);
+/* LDS-resident sorts of the envelope jobs of the last solve per draw (general envelope kernel and the cells of the tail launch), by
+ * kind: out[4*draw] = every list already in order (merge or ranks), out[4*draw+1] = a list out of order, bitonic network,
+ * out[4*draw+2] = a list out of order and the padded stream beyond the LDS capacity, counting ranks; out[4*draw+3] = those of
+ * the last two kinds in which two or more threads of the workgroup each saw a pair out of order.  Results are the same. */
+int egdst_get_sort_stats(egdst_handle *h, unsigned *out /* [4*ndraw] */);
 
 /* Envelope step of the last solve per draw: out[2*draw] = (state, period) cells completed by the throughput path (five lean
  * kernels with one wave per envelope walk, used for batches of >= 512 cells per period; environment EGDST_ENV_TP=0/1 at
